@@ -7,10 +7,13 @@ reset every stream, encode ``--tokens`` symbols per stream (integer pmf rows
 the job also gathers every rank's bitstreams over RCCL (the path's one exchange
 step).  Streams are sharded (each rank owns its own 4096), so scaling is weak.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-After the timed region (never inside it): per-stream status, a full GPU decode
+A plain run sets up, warms up, times the K jobs, writes the last job's bitstreams
+with --dump-outputs, and prints the result line (the headline figure, ms_per_step,
+and the roofline figures the timed jobs' own kernel events give).  With --full,
+after the timed region (never inside it): per-stream status, a full GPU decode
 round trip, and bit-exact parity of the packed bytes against the CPU oracle
 (oracle/, the C restatement pinned to the reference); the oracle's own time on
 the same tables is the cpu_baseline.  Rank 0 prints one JSON line.
@@ -75,6 +78,32 @@ def workload_name(V, B, world):
     return "custom"
 
 
+DUMP_LIMIT = 60 << 20          # bytes of --dump-outputs arrays (under the 64 MB a dump may take)
+
+
+def dump_outputs(coder, out_dir, suffix=""):
+    """--dump-outputs: what the last timed job gave its caller, as .npy files in `out_dir`.
+    bits<suffix>.npy: float32 [streams, stride], each stream's packed bytes (to_bytes()'s
+    format, MSB first, zero past its last bit); nbits<suffix>.npy: float64 [streams], its
+    bit count.  Streams that would pass DUMP_LIMIT are left out by a fixed seeded sample,
+    whose stream numbers go to streams<suffix>.npy."""
+    import numpy as np
+    import torch
+    bits, nbits = coder.bits_tensor(), coder.nbits_tensor()
+    torch.cuda.synchronize()
+    bits, nbits = bits.cpu().numpy(), nbits.cpu().numpy().astype(np.int64)
+    B, W = bits.shape
+    bits[np.arange(W)[None, :] >= ((nbits + 7) // 8)[:, None]] = 0
+    os.makedirs(out_dir, exist_ok=True)
+    rows = max(1, DUMP_LIMIT // (W * 4 + 16))
+    if rows < B:
+        pick = np.sort(np.random.default_rng(0).choice(B, rows, replace=False))
+        bits, nbits = bits[pick], nbits[pick]
+        np.save(os.path.join(out_dir, f"streams{suffix}.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, f"bits{suffix}.npy"), bits.astype(np.float32))
+    np.save(os.path.join(out_dir, f"nbits{suffix}.npy"), nbits.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
@@ -87,7 +116,15 @@ def main():
     ap.add_argument("--pmf-bits", type=int, default=32, choices=(32, 64))
     ap.add_argument("--scale-bits", type=int, default=0,
                     help="pmf = max(1 or 2, floor(softmax * 2^k)); 0 = 31 for u32, 60 (llama-scale) for u64")
-    ap.add_argument("--cpu-baseline", default="on", choices=("on", "off"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and side measurements: stream status, "
+                         "the timed GPU decode round trip, bit-exact parity against the CPU oracle, the "
+                         "gather check, and the cpu_baseline (a plain run stops at the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's bitstreams to DIR/bits.npy (float32 "
+                         "[streams, bytes]) and DIR/nbits.npy (float64 [streams]); with N > 1 ranks each "
+                         "rank writes its own, named bits.r<rank>.npy / nbits.r<rank>.npy")
+    ap.add_argument("--cpu-baseline", default="on", choices=("on", "off"), help="with --full")
     ap.add_argument("--cpu-threads", type=int, default=0, help="cpu_baseline threads (0 = nproc: host_cores())")
     ap.add_argument("--decode-reps", type=int, default=10,
                     help="timed decode passes, back to back, after two warm ones (the first passes after "
@@ -247,7 +284,70 @@ def main():
     cnt = (C.c_int64 * 8)()
     coder.lib.lac_profile_read(coder.ctx, C.cast(ms, C.c_void_p), C.cast(cnt, C.c_void_p), 1)
 
-    # ---------------- checks, outside the timed region
+    # ---------------- the result line: what the timed steps alone give
+    kid = 6 if cnt[6] else (4 if cnt[4] else 0)            # q1_stats, encode_fused, else row_stats
+    kname = {6: "k_q1_stats", 4: "k_encode_fused", 0: "k_row_stats"}[kid]
+    units = T * B * args.steps / max(cnt[kid], 1)           # symbols per launch of that kernel
+    rs_launch_ms = ms[kid] / max(cnt[kid], 1)
+    alg_bytes = units * (V * ebytes + 4)
+    achieved = alg_bytes / (rs_launch_ms * 1e-3) / 1e9 if cnt[kid] else None
+    rows = (f"{args.input[7:]} logit rows, q1 tables in-kernel" if logits_in else f"uint{args.pmf_bits} pmf rows")
+    cname = workload_name(V, B, world)                          # BASELINE.json configs
+    cfg = {"workload": f"{cname}: vocab={V}, {B} streams/GPU, {T} symbols/stream per job, prec={P}, {rows}",
+           "vocab": V, "streams": B, "tokens": T, "prec": P, "pmf_bits": args.pmf_bits, "input": args.input,
+           "parallelism": f"streams sharded over {world} GPU(s)" + (
+               f", {'RCCL' if backend == 'nccl' else backend} payload-sized bitstream gather to rank 0"
+               if gatherer else "")}
+    sbits = args.scale_bits or (31 if args.pmf_bits == 32 else 60)
+    line = {
+        "metric": METRIC if (V, B) == (32000, 4096) else
+                  f"encoded symbols/sec at vocab={V}, batch={B} streams; bit-exact round-trip",
+        "value": world * B * T * args.steps / dt, "unit": "symbols/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": ("u32" if logits_in else f"u{args.pmf_bits}"),
+        "data": ("synthetic: logits 3*N(0,1) (torch.Generator seeded), symbols by inverse CDF of their q1 tables"
+                 if logits_in else
+                 "synthetic: logits 3*N(0,1) per step (torch.Generator seeded 1234+t), "
+                 f"pmf=max({2 if sbits >= 60 else 1},floor(softmax*2^{sbits})), symbols by inverse CDF"),
+        "config": cfg,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                     "traffic": read_traffic(cfg, kname),
+                     "traffic_source": "not measured in this run: HBM bytes per launch of this kernel from "
+                                       "the committed profiles/pmc_traffic.json (a separate rocprofv3 --pmc "
+                                       "FETCH_SIZE pass of the same config, x2 gfx950 wide-read correction, "
+                                       "tools/pmc_traffic.py); null when no entry matches the config",
+                     "kernel": kname,
+                     "kernel_ms_per_launch": rs_launch_ms, "launches": int(cnt[kid]),
+                     "bytes_per_launch": alg_bytes,
+                     "kernel_ms_per_step": {n: ms[i] / args.steps for n, i in
+                                            (("row_stats", 0), ("encode", 1), ("finish", 2), ("encode_fused", 4),
+                                             ("q1_stats", 6))
+                                            if cnt[i]}},
+        "full": args.full,          # False: cpu_baseline and parity were not run (null below)
+        "cpu_baseline": None,
+        "parity": None,
+    }
+
+    def shutdown():
+        if gatherer:
+            coder.reset()                                  # (decoding: back to an encoder between jobs)
+            gatherer.close()
+        coder.close()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if args.dump_outputs:                                  # the last timed job coded `sym` itself
+        dump_outputs(coder, args.dump_outputs, f".r{rank}" if world > 1 else "")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        shutdown()
+        return
+
+    # ---------------- checks, outside the timed region (--full)
     gather_ok = None
     gather_info = None
     if gatherer:
@@ -399,58 +499,9 @@ def main():
         dist.barrier()                                     # ranks wait out rank 0's baseline
 
     if rank == 0:
-        kid = 6 if cnt[6] else (4 if cnt[4] else 0)        # q1_stats, encode_fused, else row_stats
-        kname = {6: "k_q1_stats", 4: "k_encode_fused", 0: "k_row_stats"}[kid]
-        units = T * B * args.steps / max(cnt[kid], 1)       # symbols per launch of that kernel
-        rs_launch_ms = ms[kid] / max(cnt[kid], 1)
-        alg_bytes = units * (V * ebytes + 4)
-        achieved = alg_bytes / (rs_launch_ms * 1e-3) / 1e9 if cnt[kid] else None
-        rows = (f"{args.input[7:]} logit rows, q1 tables in-kernel" if logits_in else f"uint{args.pmf_bits} pmf rows")
-        cname = workload_name(V, B, world)                      # BASELINE.json configs
-        cfg = {"workload": f"{cname}: vocab={V}, {B} streams/GPU, {T} symbols/stream per job, prec={P}, {rows}",
-               "vocab": V, "streams": B, "tokens": T, "prec": P, "pmf_bits": args.pmf_bits, "input": args.input,
-               "parallelism": f"streams sharded over {world} GPU(s)" + (
-                   f", {'RCCL' if backend == 'nccl' else backend} payload-sized bitstream gather to rank 0"
-                   if gatherer else "")}
-        value = world * B * T * args.steps / dt
-        line = {
-            "metric": METRIC if (V, B) == (32000, 4096) else
-                      f"encoded symbols/sec at vocab={V}, batch={B} streams; bit-exact round-trip",
-            "value": value, "unit": "symbols/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": ("u32" if logits_in else f"u{args.pmf_bits}"),
-            "data": ("synthetic: logits 3*N(0,1) (torch.Generator seeded), symbols by inverse CDF of their q1 tables"
-                     if logits_in else
-                     "synthetic: logits 3*N(0,1) per step (torch.Generator seeded 1234+t), "
-                     f"pmf=max({2 if (args.scale_bits or (31 if args.pmf_bits == 32 else 60)) >= 60 else 1},"
-                     f"floor(softmax*2^{args.scale_bits or (31 if args.pmf_bits == 32 else 60)})), symbols by inverse CDF"),
-            "config": cfg,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "traffic": read_traffic(cfg, kname),
-                         "traffic_source": "not measured in this run: HBM bytes per launch of this kernel from "
-                                           "the committed profiles/pmc_traffic.json (a separate rocprofv3 --pmc "
-                                           "FETCH_SIZE pass of the same config, x2 gfx950 wide-read correction, "
-                                           "tools/pmc_traffic.py); null when no entry matches the config",
-                         "kernel": kname,
-                         "kernel_ms_per_launch": rs_launch_ms, "launches": int(cnt[kid]),
-                         "bytes_per_launch": alg_bytes,
-                         "kernel_ms_per_step": {n: ms[i] / args.steps for n, i in
-                                                (("row_stats", 0), ("encode", 1), ("finish", 2), ("encode_fused", 4),
-                                                 ("q1_stats", 6))
-                                                if cnt[i]}},
-            "cpu_baseline": cpu,
-            "parity": parity,
-        }
+        line.update({"cpu_baseline": cpu, "parity": parity})
         print(json.dumps(line), flush=True)
-    if gatherer:
-        coder.reset()                                      # (decoding: back to an encoder between jobs)
-        gatherer.close()
-    coder.close()
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    shutdown()
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 """Per-launch HBM read traffic from a rocprofv3 --pmc FETCH_SIZE run.
 
     rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc -o run --output-format csv \
-        -- python3 bench.py --steps 3 --warmup 1 --cpu-baseline off
+        -- python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline off
     python tools/pmc_traffic.py gpurun_out/pmc [--input pmf|logits-bf16|logits-f32] [--vocab V --tokens T]
         (adds / replaces this configuration's entry in profiles/pmc_traffic.json)
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise an A/B directory of bench JSON lines: value, roofline frac and decode rate per file."""
+"""Summarise an A/B directory of `bench.py --full` JSON lines: value, roofline frac and decode rate per file."""
 import glob
 import json
 import os

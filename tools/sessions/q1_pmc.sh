@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/q1pmc
-ARGS="${ARGS:---input logits-bf16}"
+ARGS="--full ${ARGS:---input logits-bf16}"    # --full: the decode kernels run after the timed jobs
 timeout -k 10 120 rocprofv3 -L > gpurun_out/q1pmc/counters.txt 2>&1 || true
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES" \

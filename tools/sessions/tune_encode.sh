@@ -33,7 +33,7 @@ mkdir -p gpurun_out/tune
 for rep in 1 2; do
   for so in tools/tune/liblac_*.so; do
     v=$(basename "$so" .so)
-    LAC_LIB="$PWD/$so" timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-baseline off "$@" \
+    LAC_LIB="$PWD/$so" timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline off "$@" \
         > "gpurun_out/tune/$v.$rep.json" 2> "gpurun_out/tune/$v.$rep.err"
     rc=$?
     [ $rc -ne 0 ] && { echo "$v rc=$rc"; tail -5 "gpurun_out/tune/$v.$rep.err"; exit $rc; }
