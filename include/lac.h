@@ -153,6 +153,41 @@ int lac_close(lac_ctx *ctx);
 /* Tune a context (LAC_OPT_*); results are identical on every path. */
 int lac_set_option(lac_ctx *ctx, int option, int64_t value);
 
+/* Per-stream symbol counts: streams of different lengths in one batch.  len_dev: int64[streams]
+ * in device memory, copied into the context on `stream` (the caller's buffer is not borrowed);
+ * NULL clears.  While set, stream b takes part in a step only while the symbols it has coded
+ * since the last reset / lac_decode_open (EncState.nsym / DecState.nsym) number fewer than
+ * len[b] -- the base is that count, not the step index of a call, so encoding in calls of 50 +
+ * 80 steps equals one call of 130.  For a stream that has reached its count a step is a no-op:
+ * its state, planes, status and nsym do not change and it raises no error; encode does not
+ * inspect its sym entry or write its trace entry; decode writes -1 to its sym_out entry.  The
+ * memory of its table or logits row must be addressable, but the row's contents are never
+ * observable: not in any stream's bits, outputs, status or registers.  A count <= 0 ends the
+ * stream from the start (its finish is the flush of a fresh state, as a zero-symbol job's); a
+ * count larger than the steps given is simply not reached.  Counts persist across
+ * lac_encode_reset, the jobs' implicit reset and lac_decode_open, and are no part of
+ * lac_enc_state / lac_dec_state.  With LAC_OPT_DECODE_STOP a stream stops at whichever comes
+ * first; reaching the count leaves status 0.  With no counts set every result is what it was.
+ *
+ * Which kernels skip a dead row (never fetch it) and which merely ignore it:
+ *   skip    k_encode_fused (loop and prefetch bound), k_row_stats, k_encode; k_decode_wave,
+ *           k_decode_wave_fine, k_decode_block, k_decode_step, k_dec_stats, k_decode_seq; the
+ *           coder kernels of the logits path (k_encode over the q1 statistics, k_q1_decode)
+ *   ignore  the q1 row-statistics kernels of the logits path (k_q1_stats, _rl, _wide, single
+ *           block and row group forms): a dead logits row is read and quantised like any other
+ *           -- whatever it holds (zeros, NaN) raises nothing -- and its statistics are never
+ *           consumed.  No participant of a row group's exchange leaves early.  So on the
+ *           logits path counts save the coder kernels' work but no row traffic: every padded
+ *           row is still fetched once by these kernels, and their encode form also loads the
+ *           dead step's sym entry (clamped into [0, V], used for nothing that is consumed).
+ *           Skipping dead rows in their single-block forms is open work.
+ *   route   few-stream decodes take k_decode_seq instead of the lean step (k_decode_lean and its
+ *           prefetching helpers know no counts), as LAC_OPT_DECODE_STOP takes the stats path.
+ * lac_decode_tail_begin / lac_decode_tail_step (one stream's tail in the reference frame)
+ * return LAC_E_STATE while counts are set; lac_quantize_logits materialises tables and ignores
+ * counts. */
+int lac_set_stream_lengths(lac_ctx *ctx, const int64_t *len_dev, void *stream);
+
 /* Reset every stream to l = 0, h = 2^prec - 1 with an empty output. */
 int lac_encode_reset(lac_ctx *ctx, void *stream);
 

@@ -43,6 +43,7 @@ PROTOTYPES = [
     ("lac_last_error", C.c_char_p, []),
     ("lac_open", _i, [_i, _i, _i64, _i64, _i, _u64, C.POINTER(_vp)]),
     ("lac_close", _i, [_vp]),
+    ("lac_set_stream_lengths", _i, [_vp, _vp, _vp]),
     ("lac_encode_reset", _i, [_vp, _vp]),
     ("lac_encode", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     ("lac_encode_job", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),

@@ -249,7 +249,39 @@ class BatchCoder:
         check(self.lib.lac_encode_set_state(self.ctx, st.ctypes.data_as(C.c_void_p),
                                             planes.ctypes.data_as(C.c_void_p), self._stream))
 
+    def set_stream_lengths(self, lengths):
+        """Per-stream symbol counts (include/lac.h lac_set_stream_lengths): stream b codes
+        only its first ``lengths[b]`` symbols -- counted since the last reset / decode_open,
+        over any number of calls -- and every later step is a no-op for it: nothing of its
+        row or symbol is read, encode writes no trace entry, decode writes -1.  ``lengths``:
+        a sequence, numpy array or tensor of ``streams`` integers >= 0; None clears.  The
+        values are copied (uploaded as int64), nothing is borrowed; they persist across
+        reset, the jobs and decode_open.  Not to be confused with :meth:`lengths`, the
+        encoded bit counts."""
+        if lengths is None:
+            check(self.lib.lac_set_stream_lengths(self.ctx, None, self._stream))
+            return
+        torch = _torch()
+        if isinstance(lengths, torch.Tensor):
+            lengths = lengths.detach().cpu().numpy()
+        n = np.asarray(lengths)
+        if n.shape != (self.streams,):
+            raise ValueError(f"lengths must have shape [{self.streams}], got {list(n.shape)}")
+        if n.dtype.kind not in "iu":
+            raise TypeError(f"lengths must be integers, got {n.dtype}")
+        if n.size and int(n.min()) < 0:
+            raise ValueError("lengths must be >= 0")
+        if n.size and int(n.max()) > np.iinfo(np.int64).max:
+            raise ValueError("lengths must fit int64")
+        dev = torch.from_numpy(np.ascontiguousarray(n, dtype=np.int64)).to(self.device)
+        check(self.lib.lac_set_stream_lengths(self.ctx, C.c_void_p(dev.data_ptr()), self._stream))
+        # the library copies on the stream: keep the staging tensor until that copy is queued
+        # behind everything else (the caching allocator reuses it in stream order)
+        self._len_keep = dev
+
     def lengths(self):
+        """Encoded bit counts per stream (after finish / a job).  The per-stream *symbol*
+        counts of ragged batches are :meth:`set_stream_lengths`."""
         n = np.zeros(self.streams, dtype=np.uint64)
         check(self.lib.lac_encoded_lengths(self.ctx, n.ctypes.data_as(C.c_void_p), self._stream))
         return n

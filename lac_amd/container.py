@@ -78,23 +78,36 @@ def _is_logits(tables):
     return tables.dtype in (torch.bfloat16, torch.float32)
 
 
-def compress_batch(coder, pmf, sym) -> bytes:
+def compress_batch(coder, pmf, sym, n_symbols=None) -> bytes:
     """Encode a batch with a BatchCoder and wrap it in a container.  ``pmf``:
-    integer tables (one lac_encode_job) or bf16/f32 logits (the q1 logits path)."""
+    integer tables (one lac_encode_job) or bf16/f32 logits (the q1 logits path).
+    ``n_symbols`` (a sequence of ``streams`` counts in [0, steps]): stream b codes only its
+    first n_symbols[b] symbols (BatchCoder.set_stream_lengths, left set on the coder) and the
+    header records those counts.  None leaves the coder as it is and records ``steps`` for
+    every stream, which is right for a coder with no counts set: clear counts set earlier
+    (``coder.set_stream_lengths(None)``) or pass them here."""
     logits = _is_logits(pmf)
+    steps = sym.shape[0]
+    if n_symbols is None:
+        counts = [steps] * coder.streams
+    else:
+        counts = [int(n) for n in n_symbols]
+        if len(counts) != coder.streams or any(n < 0 or n > steps for n in counts):
+            raise ValueError(f"n_symbols: {coder.streams} counts in [0, {steps}]")
+        coder.set_stream_lengths(counts)
     if logits:
         coder.encode_logits_job(pmf, sym)
     else:
         coder.encode_job(pmf, sym)
     data, nbits = coder.to_bytes()
-    steps = sym.shape[0]
-    return pack(data, [steps] * coder.streams, [int(x) for x in nbits], coder.prec, coder.vocab,
+    return pack(data, counts, [int(x) for x in nbits], coder.prec, coder.vocab,
                 pmf_bits=coder.pmf_bits, q1_logits=logits)
 
 
 def decompress_batch(blob: bytes, pmf, device=None):
     """Decode a container produced by :func:`compress_batch` given the same tables
-    (the same logits for a q1 container)."""
+    (the same logits for a q1 container).  -> (out [max(n_symbols), streams] int32, n_symbols);
+    where the streams' counts differ, out is -1 past each stream's count."""
     import numpy as np
     import torch
 
@@ -111,6 +124,9 @@ def decompress_batch(blob: bytes, pmf, device=None):
     coder.set_mapping(h["mapping"])
     bits = torch.from_numpy(buf).to(coder.device)
     nb = torch.tensor(h["n_bits"], dtype=torch.int64, device=coder.device)
+    # a ragged container: each stream decodes its own count and no further (out is -1 past it)
+    if any(n != steps for n in h["n_symbols"]):
+        coder.set_stream_lengths(h["n_symbols"])
     coder.decode_open(bits, nb)
     if h["q1_logits"] != _is_logits(pmf):
         raise ValueError("container and tables disagree: q1 logits vs integer pmf")

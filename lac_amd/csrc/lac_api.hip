@@ -94,6 +94,7 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->lwin);
     (void)hipFree(c->q1m);
     (void)hipFree(c->pxch);
+    (void)hipFree(c->slen);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;
@@ -141,6 +142,21 @@ int lac_set_option(lac_ctx *c, int option, int64_t value) {
     default:
         return fail(LAC_E_ARG, "unknown option %d", option);
     }
+}
+
+int lac_set_stream_lengths(lac_ctx *c, const int64_t *len_dev, void *stream) {
+    if (!c) return fail(LAC_E_ARG, "ctx is NULL");
+    if (!len_dev) {
+        c->has_len = false;
+        return LAC_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->slen) HIPCHK(hipMalloc(&c->slen, sizeof(int64_t) * c->B));
+    // the context's own copy, ordered on `stream` before every later launch there: the
+    // caller's buffer is not borrowed
+    HIPCHK(hipMemcpyAsync(c->slen, len_dev, sizeof(int64_t) * c->B, hipMemcpyDeviceToDevice, S(stream)));
+    c->has_len = true;
+    return LAC_OK;
 }
 
 int lac_stream_status(lac_ctx *c, int32_t *err_host, int64_t *err_step_host, void *stream) {

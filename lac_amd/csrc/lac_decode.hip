@@ -20,14 +20,15 @@ __global__ __launch_bounds__(64 * NW) void k_decode_step(const E *__restrict__ p
                                                          int64_t stream_stride, int64_t V, int prec,
                                                          DecState *states, const uint8_t *bits, uint64_t stride,
                                                          const uint64_t *nbits, int32_t *sym_out, int64_t B,
-                                                         int mapping) {
+                                                         int mapping, const int64_t *__restrict__ slen) {
     extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
     __shared__ uint64_t wmin[NW];
     __shared__ uint32_t wovf[NW];
     const int lane = (int)lane_id(), wave = threadIdx.x >> 6;
     const int64_t b = blockIdx.x;
     DecState st = states[b];
-    if (st.err) {
+    // failed, stopped, or at its count (lac_set_stream_lengths): -1, nothing else changes
+    if (st.err || live_steps(slen, b, st.nsym, 1) == 0) {
         if (threadIdx.x == 0) sym_out[b] = -1;
         return;
     }
@@ -127,7 +128,7 @@ __global__ LAC_DEC_BOUNDS void k_decode_wave(const E *__restrict__ pmf, int64_t 
                                                      int64_t stream_stride, int64_t nsteps, int64_t V, int prec,
                                                      DecState *states, const uint8_t *bits, uint64_t stride,
                                                      const uint64_t *nbits, int32_t *sym_out, int64_t B,
-                                                     int mapping) {
+                                                     int mapping, const int64_t *__restrict__ slen) {
     const int lane = (int)lane_id();
     const int64_t b = (int64_t)blockIdx.x * kStreamWaves + wave_in_block();
     if (b >= B) return;
@@ -139,6 +140,13 @@ __global__ LAC_DEC_BOUNDS void k_decode_wave(const E *__restrict__ pmf, int64_t 
     int64_t CI = (nit + 63) / 64;                             // iterations per chunk: <= 64 chunks
     CI = ((CI + U - 1) / U) * U;
     const int64_t nch = (nit + CI - 1) / CI;
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch (a
+    // scalar bound), -1 for the rest
+    const int64_t nall = nsteps;
+    if (slen) {
+        nsteps = live_steps(slen, b, st.nsym, nall);
+        for (int64_t j = nsteps + lane; j < nall; j += 64) sym_out[j * B + b] = -1;
+    }
     for (int64_t t = 0; t < nsteps; t++) {
         int32_t *out = sym_out + t * B + b;
         if (st.err) {
@@ -328,7 +336,8 @@ template <typename E, int VEC, int NR>
 __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wave_fine(const E *__restrict__ pmf, int64_t step_stride,
                                                   int64_t stream_stride, int64_t nsteps, int64_t V, int prec,
                                                   DecState *states, const uint8_t *bits, uint64_t stride,
-                                                  const uint64_t *nbits, int32_t *sym_out, int64_t B, int mapping) {
+                                                  const uint64_t *nbits, int32_t *sym_out, int64_t B, int mapping,
+                                                  const int64_t *__restrict__ slen) {
     constexpr bool W = sizeof(E) == 8;
     const int lane = (int)lane_id();
     const int64_t b = (int64_t)blockIdx.x * kStreamWaves + wave_in_block();
@@ -337,6 +346,13 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
     const uint8_t *mybits = bits + b * stride;
     const uint64_t mynbits = nbits[b];
     const int nvec = (int)(V / VEC), nit = (nvec + 63) / 64, ngrp = (nit + 7) / 8;
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch (a
+    // scalar bound for the loop and its prefetches), -1 for the rest
+    const int64_t nall = nsteps;
+    if (slen) {
+        nsteps = live_steps(slen, b, st.nsym, nall);
+        for (int64_t j = nsteps + lane; j < nall; j += 64) sym_out[j * B + b] = -1;
+    }
 #if LAC_DEC_XPF
     // XD = 2: two groups in flight (g + 1 and g + 2) while group g is summed, and the
     // next row's groups 0 and 1 over the step's tail; rows of <= 128 iterations (u64:
@@ -498,17 +514,23 @@ __global__ __launch_bounds__(64 * NW) void k_decode_block(const E *__restrict__ 
                                                           int64_t stream_stride, int64_t nsteps, int64_t V, int prec,
                                                           DecState *states, const uint8_t *bits, uint64_t stride,
                                                           const uint64_t *nbits, int32_t *sym_out, int64_t B,
-                                                          int mapping) {
+                                                          int mapping, const int64_t *__restrict__ slen) {
     constexpr bool W = sizeof(E) == 8;
     constexpr int S = NW - 1, NRMAX = 8;                      // streamer waves; <= 512 iterations per row
     __shared__ uint64_t tot[2][64 * NRMAX];
     __shared__ uint64_t smin[2][S];
     __shared__ uint32_t sovf[2][S];
     __shared__ int32_t serr;
+    __shared__ int64_t slive;
     const int lane = (int)lane_id(), w = wave_in_block();
     const int64_t b = blockIdx.x;
     const int nvec = (int)(V / VEC), nit = (nvec + 63) / 64, ngrp = (nit + 7) / 8;
-    if (threadIdx.x == 0) serr = states[b].err;
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch,
+    // one value for the whole workgroup -- every wave runs the same number of barriers
+    if (threadIdx.x == 0) {
+        serr = states[b].err;
+        slive = live_steps(slen, b, states[b].nsym, nsteps);
+    }
 
     // streamer s (1..S): groups s-1, s-1+S, ... of step t into buffer t & 1
     auto stream_row = [&](int64_t t) {
@@ -553,6 +575,10 @@ __global__ __launch_bounds__(64 * NW) void k_decode_block(const E *__restrict__ 
     if (w == 0) { st = states[b]; mynbits = nbits[b]; }
     __syncthreads();
     const bool dead = serr != 0;                              // an errored stream stays errored
+    const int64_t nall = nsteps;
+    nsteps = (int64_t)rfl_u64((uint64_t)slive);               // (workgroup-uniform; <= nall)
+    if (w == 0)                                                // past the stream's count: -1
+        for (int64_t j = nsteps + lane; j < nall; j += 64) sym_out[j * B + b] = -1;
     if (w > 0 && !dead && nsteps > 0) stream_row(0);
     __syncthreads();
     for (int64_t t = 0; t < nsteps; t++) {
@@ -692,11 +718,16 @@ __global__ __launch_bounds__(256) void k_dec_stats(const E *__restrict__ pmf, in
                                                    int64_t t0, uint64_t *__restrict__ chunks,
                                                    DecRowMeta *__restrict__ meta, E *__restrict__ lcdf = nullptr,
                                                    uint64_t *__restrict__ lchunk = nullptr,
-                                                   LeanMeta *__restrict__ lmeta = nullptr) {
+                                                   LeanMeta *__restrict__ lmeta = nullptr,
+                                                   const DecState *states = nullptr,
+                                                   const int64_t *__restrict__ slen = nullptr) {
     typedef typename VecT<E, VEC>::type Vt;
     const int lane = (int)lane_id();
     const int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (r >= rows) return;
+    // a row past its stream's count (lac_set_stream_lengths) is neither read nor written:
+    // k_decode_seq stops before it
+    if (slen && !live_row(slen, r % B, states[r % B].nsym, r / B)) return;
     const E *row = pmf + (t0 + r / B) * step_stride + (r % B) * stream_stride;
     constexpr bool W = sizeof(E) == 8;
     const int64_t nvec = V / VEC, nit = (nvec + 63) / 64, ngrp = (nit + 7) / 8;
@@ -829,7 +860,8 @@ __global__ __launch_bounds__(256) void k_decode_seq(const E *__restrict__ pmf, i
                                             const uint8_t *bits, uint64_t stride, const uint64_t *nbits,
                                             int32_t *sym_out, int64_t B, int mapping,
                                             int64_t *__restrict__ resume = nullptr, int64_t rstep = -1,
-                                            int stop_undet = 0, int64_t max_steps = INT64_MAX) {
+                                            int stop_undet = 0, int64_t max_steps = INT64_MAX,
+                                            const int64_t *__restrict__ slen = nullptr) {
     const int lane = (int)lane_id();
     // rows of statistics per step: B, or 0 for a static model (stride-0 steps: one row per stream)
     if (rstep < 0) rstep = B;
@@ -849,7 +881,14 @@ __global__ __launch_bounds__(256) void k_decode_seq(const E *__restrict__ pmf, i
     if (i0 >= nsteps) return;
     // max_steps: only that many -- the step a lean launch left at; resume[b] then moves past
     // them and the next lean launch goes on from there
-    const int64_t iend = max_steps < nsteps - i0 ? i0 + max_steps : nsteps;
+    int64_t iend = max_steps < nsteps - i0 ? i0 + max_steps : nsteps;
+    // per-stream counts (lac_set_stream_lengths; the launcher then runs no lean step, so
+    // i0 = 0): the stream's live steps of this launch (a scalar bound), -1 for the rest
+    if (slen) {
+        iend = live_steps(slen, b, st.nsym, iend);
+        for (int64_t j = iend + lane; j < nsteps; j += 64) sym_out[(t0 + j) * B + b] = -1;
+        if (iend == 0) return;
+    }
     uint64_t next = chunks[(i0 * rstep + b) * 64 + lane];
     DecRowMeta nmeta = meta[i0 * rstep + b];
 #if LAC_DEC_PHASES
@@ -1399,11 +1438,11 @@ static int decode_launch(lac_ctx *c, const E *pmf, int64_t step_off, int64_t str
     if (c->B <= 256)        // few streams: 16 waves per stream keep the whole row in flight
         k_decode_step<E, VEC, G, 16><<<(unsigned)c->B, 64 * 16, lds, st>>>(
             pmf, step_off, stream_stride, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping);
+            c->mapping, stream_lengths(c));
     else
         k_decode_step<E, VEC, G, kWavesPerBlock><<<(unsigned)c->B, 64 * kWavesPerBlock, lds, st>>>(
             pmf, step_off, stream_stride, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping);
+            c->mapping, stream_lengths(c));
     CHECK_LAUNCH();
     return LAC_OK;
 }
@@ -1417,7 +1456,7 @@ static int decode_wave_launch(lac_ctx *c, const E *pmf, int64_t step_stride, int
 #define LAC_FINE(NR)                                                                                              \
     k_decode_wave_fine<E, VEC, NR><<<blocks, 64 * kStreamWaves, 0, st>>>(                                        \
         pmf, step_stride, stream_stride, steps, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B, \
-        c->mapping)
+        c->mapping, stream_lengths(c))
     bool fine = false;
     if constexpr (VEC > 1) {
         fine = c->fine_decode && nit <= 512;
@@ -1428,7 +1467,7 @@ static int decode_wave_launch(lac_ctx *c, const E *pmf, int64_t step_stride, int
     if (!fine)
         k_decode_wave<E, VEC><<<blocks, 64 * kStreamWaves, 0, st>>>(
             pmf, step_stride, stream_stride, steps, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping);
+            c->mapping, stream_lengths(c));
 #undef LAC_FINE
     CHECK_LAUNCH();
     return LAC_OK;
@@ -1464,7 +1503,11 @@ static int decode_stats_path(lac_ctx *c, const E *pmf, int64_t step_stride, int6
     // 5.39 vs 5.26; profiles/r04/lean/fewstreams/)
     const int64_t wstride = (int64_t)(c->dstride / 8) + 2;     // k_lean_window's words per stream
     bool lean = false;
-    if constexpr (VEC > 1) lean = LAC_LEAN && c->prec <= 50 && CI <= 4 && nvec > 0 && c->B <= kLeanMaxStreams;
+    // Per-stream counts (lac_set_stream_lengths) take k_decode_seq, as LAC_OPT_DECODE_STOP takes
+    // this path: the lean step and its prefetching helpers stay unaware of counts, so no
+    // helper waits on a decoder that has left at its count.
+    if constexpr (VEC > 1)
+        lean = LAC_LEAN && c->prec <= 50 && CI <= 4 && nvec > 0 && c->B <= kLeanMaxStreams && !c->has_len;
     int64_t cs = stat ? steps : c->chunk_steps;
     if (lean) {
         const int64_t rows_fit = kLeanBytes / (c->V * (int64_t)sizeof(E));
@@ -1556,12 +1599,14 @@ static int decode_stats_path(lac_ctx *c, const E *pmf, int64_t step_stride, int6
         }
         if (!lean && fresh) {
             k_dec_stats<E, VEC><<<sblocks, 64 * kWavesPerBlock, 0, st>>>(
-                pmf, step_stride, stream_stride, c->B, rows, c->V, t0, c->q1chunks, (DecRowMeta *)c->dmeta);
+                pmf, step_stride, stream_stride, c->B, rows, c->V, t0, c->q1chunks, (DecRowMeta *)c->dmeta, nullptr,
+                nullptr, nullptr, c->dec, stream_lengths(c));
             CHECK_LAUNCH();
         }
         k_decode_seq<E, VEC><<<blocks, 64 * kWavesPerBlock, 0, st>>>(
             pmf, step_stride, stream_stride, t0, n, c->V, c->prec, c->q1chunks, (const DecRowMeta *)c->dmeta, c->dec,
-            c->dbits, c->dstride, c->dnbits, out, c->B, c->mapping, lean ? c->dresume : nullptr, rstep, c->dec_stop);
+            c->dbits, c->dstride, c->dnbits, out, c->B, c->mapping, lean ? c->dresume : nullptr, rstep, c->dec_stop,
+            INT64_MAX, stream_lengths(c));
         CHECK_LAUNCH();
     }
     return LAC_OK;
@@ -1575,7 +1620,7 @@ static int decode_block_launch(lac_ctx *c, const E *pmf, int64_t step_stride, in
 #define LAC_BLK(NW)                                                                                              \
     k_decode_block<E, VEC, NW><<<(unsigned)c->B, 64 * NW, 0, st>>>(pmf, step_stride, stream_stride, steps, c->V,  \
                                                                   c->prec, c->dec, c->dbits, c->dstride, c->dnbits, \
-                                                                  out, c->B, c->mapping)
+                                                                  out, c->B, c->mapping, stream_lengths(c))
     if (nw == 4) LAC_BLK(4);
     else if (nw == 8) LAC_BLK(8);
     else LAC_BLK(16);
@@ -1725,6 +1770,8 @@ int lac_decode_determined(lac_ctx *c, int64_t *ndet_host, void *stream) {
 int lac_decode_tail_begin(lac_ctx *c, void *stream) {
     if (!c) return fail(LAC_E_ARG, "ctx is NULL");
     if (c->mode != 1) return fail(LAC_E_STATE, "call lac_decode_open first");
+    if (c->has_len) return fail(LAC_E_STATE, "the decoder tail knows no per-stream counts: clear them first "
+                                             "(lac_set_stream_lengths with NULL)");
     HIPCHK(hipSetDevice(c->device));
     if (!c->tail) HIPCHK(hipMalloc(&c->tail, sizeof(TailState) * c->B));
     k_decode_tail_begin<<<(unsigned)((c->B + 255) / 256), 256, 0, S(stream)>>>(c->dec, c->dnbits, c->B, c->prec,
@@ -1736,6 +1783,8 @@ int lac_decode_tail_begin(lac_ctx *c, void *stream) {
 int lac_decode_tail_step(lac_ctx *c, const void *pmf_dev, int64_t stream_stride, int mode, int64_t *sym_out_dev,
                          int32_t *code_out_dev, void *stream) {
     if (!c || !sym_out_dev || !code_out_dev) return fail(LAC_E_ARG, "NULL argument");
+    if (c->has_len) return fail(LAC_E_STATE, "the decoder tail knows no per-stream counts: clear them first "
+                                             "(lac_set_stream_lengths with NULL)");
     if (!c->tail) return fail(LAC_E_STATE, "call lac_decode_tail_begin (or lac_decode_tail_set_state) first");
     if (mode != LAC_TAIL_DECIDE && mode != LAC_TAIL_FLUSH) return fail(LAC_E_ARG, "bad tail mode %d", mode);
     if (c->mapping == LAC_MAP_CEIL && !pmf_dev) return fail(LAC_E_ARG, "pmf_dev is NULL");

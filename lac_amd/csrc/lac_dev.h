@@ -105,6 +105,29 @@ __device__ inline uint64_t rfl_u64(uint64_t x) {          // a wave-uniform valu
            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
 }
 
+// Per-stream symbol counts (lac_set_stream_lengths): how many of a launch's `nsteps` steps
+// stream b still takes part in -- its count less the `nsym` symbols it has coded, clamped to
+// [0, nsteps]; nsteps when no counts are set (slen == nullptr).  Wave-uniform where b and
+// nsym are (an SGPR loop bound: the new test is a scalar compare).
+__device__ inline int64_t live_steps(const int64_t *slen, int64_t b, int64_t nsym, int64_t nsteps) {
+    if (!slen) return nsteps;
+    const int64_t n = (int64_t)rfl_u64((uint64_t)slen[b]);
+    nsym = (int64_t)rfl_u64((uint64_t)nsym);
+    if (n <= nsym) return 0;                                  // (nsym >= 0: n - nsym cannot overflow)
+    return n - nsym < nsteps ? n - nsym : nsteps;
+}
+// The same test for one row of a row-statistics launch: row i of the chunk is live iff
+// nsym + i < slen[b], nsym read at the chunk's start (the previous chunk's coder kernel has
+// finished on the same HIP stream).  One wave owns the row, so b, nsym and i are
+// wave-uniform: moved to SGPRs, the test is a scalar compare.
+__device__ inline bool live_row(const int64_t *slen, int64_t b, int64_t nsym, int64_t i) {
+    if (!slen) return true;
+    const int64_t n = (int64_t)rfl_u64((uint64_t)slen[b]);
+    nsym = (int64_t)rfl_u64((uint64_t)nsym);
+    i = (int64_t)rfl_u64((uint64_t)i);
+    return n > nsym && i < n - nsym;
+}
+
 __device__ inline uint64_t shfl_u64(uint64_t v, int src) {
     const uint32_t lo = __shfl((int)(uint32_t)v, src), hi = __shfl((int)(uint32_t)(v >> 32), src);
     return ((uint64_t)hi << 32) | lo;

@@ -31,11 +31,15 @@ template <typename E, int VEC>
 __global__ __launch_bounds__(256) void k_row_stats(const E *__restrict__ pmf, int64_t step_stride,
                                                    int64_t stream_stride, const int32_t *__restrict__ sym,
                                                    int64_t B, int64_t rows, int64_t V, int64_t t0,
-                                                   RowStats *__restrict__ out) {
+                                                   RowStats *__restrict__ out, const EncState *states,
+                                                   const int64_t *__restrict__ slen) {
     const int lane = (int)lane_id();
     const int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int64_t t = t0 + r / B, b = r % B;
+    // a row past its stream's count (lac_set_stream_lengths) is neither read nor written:
+    // k_encode stops before it
+    if (slen && !live_row(slen, b, states[b].nsym, r / B)) return;
     const RowSums rs = row_reduce<E, VEC>(pmf + t * step_stride + b * stream_stride, V, sym[t * B + b]);
     if (lane == 0) {
         RowStats st;
@@ -161,13 +165,19 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
                                                 int64_t step_stride, int64_t stream_stride, int64_t V, int prec,
                                                 EncState *states, uint64_t *planeA, uint64_t *planeC,
                                                 uint64_t cap_words, uint64_t *trace, int mapping,
-                                                bool allow_fudge) {
+                                                bool allow_fudge, const int64_t *__restrict__ slen) {
     const int lane = (int)lane_id();
     // (the stream index provably wave-uniform: the row and trace addresses -- and the
     // per-step trace test -- stay on the scalar unit)
     const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + wave_in_block();
     if (b >= B) return;
     EncState st = states[b];
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch
+    // (a scalar); an ended stream changes nothing, raises nothing
+    if (slen) {
+        nsteps = live_steps(slen, b, st.nsym, nsteps);
+        if (nsteps == 0) return;
+    }
     if (st.err || st.nflush >= 0) {
         if (lane == 0 && !st.err && st.nflush >= 0) { st.err = LAC_E_STATE; st.err_step = st.nsym; states[b] = st; }
         return;
@@ -361,12 +371,15 @@ __global__ LAC_ENC_BOUNDS void k_encode_fused(const E *__restrict__ pmf, int64_t
                                                       int64_t B, int64_t t0, int64_t nsteps, int64_t V, int prec,
                                                       EncState *states, uint64_t *planeA, uint64_t *planeC,
                                                       uint64_t cap_words, uint64_t *trace, uint64_t *nbits, int flags,
-                                                      int mapping, int term) {
+                                                      int mapping, int term, const int64_t *__restrict__ slen) {
     const int lane = (int)lane_id();
     const int64_t b = (int64_t)blockIdx.x * kStreamWaves + (threadIdx.x >> 6);
     if (b >= B) return;
     EncState st = (flags & kReset) ? fresh_state(prec) : states[b];
     uint64_t *pa = planeA + (uint64_t)b * cap_words, *pc = planeC + (uint64_t)b * cap_words;
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch, a
+    // scalar loop bound -- rows past it are neither prefetched nor read
+    if (slen) nsteps = live_steps(slen, b, st.nsym, nsteps);
     if (st.err || st.nflush >= 0) {
         if (!st.err && st.nflush >= 0 && nsteps > 0) { st.err = LAC_E_STATE; st.err_step = st.nsym; }
         if (lane == 0) {
@@ -528,7 +541,7 @@ static int encode_impl(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t st
         ProfScope ps(c, KID_FUSED, st);
         k_encode_fused<E, VEC><<<(unsigned)((c->B + kStreamWaves - 1) / kStreamWaves), 64 * kStreamWaves, 0, st>>>(
             pmf, step_stride, stream_stride, sym, c->B, 0, steps, c->V, c->prec, c->enc, c->planeA, c->planeC,
-            c->cap_words, trace, c->nbits, flags, c->mapping, c->term);
+            c->cap_words, trace, c->nbits, flags, c->mapping, c->term, stream_lengths(c));
         CHECK_LAUNCH();
         return LAC_OK;
     }
@@ -542,7 +555,8 @@ static int encode_impl(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t st
         {
             ProfScope ps(c, KID_ROW_STATS, st);
             k_row_stats<E, VEC><<<(unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock), 64 * kWavesPerBlock, 0,
-                                  st>>>(pmf, step_stride, stream_stride, sym, c->B, rows, c->V, t0, c->stats);
+                                  st>>>(pmf, step_stride, stream_stride, sym, c->B, rows, c->V, t0, c->stats, c->enc,
+                                        stream_lengths(c));
         }
         CHECK_LAUNCH();
         {
@@ -550,11 +564,11 @@ static int encode_impl(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t st
             if (c->mapping == LAC_MAP_FLOOR)
                 k_encode<E, LAC_MAP_FLOOR><<<blocks, 64 * kWavesPerBlock, 0, st>>>(
                     c->stats, sym, c->B, t0, n, pmf, step_stride, stream_stride, c->V, c->prec, c->enc, c->planeA,
-                    c->planeC, c->cap_words, trace, c->mapping, true);
+                    c->planeC, c->cap_words, trace, c->mapping, true, stream_lengths(c));
             else
                 k_encode<E, LAC_MAP_CEIL><<<blocks, 64 * kWavesPerBlock, 0, st>>>(
                     c->stats, sym, c->B, t0, n, pmf, step_stride, stream_stride, c->V, c->prec, c->enc, c->planeA,
-                    c->planeC, c->cap_words, trace, c->mapping, true);
+                    c->planeC, c->cap_words, trace, c->mapping, true, stream_lengths(c));
         }
         CHECK_LAUNCH();
     }
@@ -605,7 +619,7 @@ int enc_stats_launch(lac_ctx *c, const int32_t *sym, int64_t t0, int64_t n, uint
         ProfScope ps(c, KID_ENCODE, st);
         k_encode<uint32_t, LAC_MAP_CEIL><<<blocks, 64 * kWavesPerBlock, 0, st>>>(
             c->stats, sym, c->B, t0, n, (const uint32_t *)nullptr, 0, 0, c->V, c->prec, c->enc, c->planeA,
-            c->planeC, c->cap_words, trace, LAC_MAP_CEIL, false);
+            c->planeC, c->cap_words, trace, LAC_MAP_CEIL, false, stream_lengths(c));
     }
     CHECK_LAUNCH();
     return LAC_OK;

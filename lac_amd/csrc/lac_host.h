@@ -62,6 +62,8 @@ struct lac_ctx {
     float *q1m = nullptr;               //                [chunk_steps * B] row maxima
     uint64_t *pxch = nullptr;           // paired row stats (shape 19): [2 * cus] maximum words
     int64_t xch_abort = -1;             // word of pxch holding the last row-group launch's abort flag
+    int64_t *slen = nullptr;            // lac_set_stream_lengths: [B] per-stream symbol counts (the context's copy)
+    bool has_len = false;               //                         counts are set (kernels get slen, else nullptr)
     // live kernel timing (lac_profile_enable): hipEvent pairs around launches
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -115,6 +117,10 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 #define CHECK_LAUNCH() HIPCHK(hipGetLastError())
 
 static inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The per-stream symbol counts as the kernels take them: null while none are set, so every
+// kernel then computes what it did before counts existed.
+static inline const int64_t *stream_lengths(const lac_ctx *c) { return c->has_len ? c->slen : nullptr; }
 
 // Encode bookkeeping for lac_set_output / lac_pack_bits: a call that coded symbols leaves the
 // streams open; a job or finish closes them and records which buffers hold the result.

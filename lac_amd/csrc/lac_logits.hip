@@ -1562,7 +1562,8 @@ __global__ LAC_DEC_BOUNDS void k_q1_decode(const LT *__restrict__ lg, int64_t st
                                            int64_t t0, int64_t nsteps, int64_t V, int prec, uint32_t xsh,
                                            int64_t Garg, const uint64_t *__restrict__ chunks,
                                            const float *__restrict__ mrow, DecState *states, const uint8_t *bits,
-                                           uint64_t stride, const uint64_t *nbits, int32_t *sym_out, int64_t B) {
+                                           uint64_t stride, const uint64_t *nbits, int32_t *sym_out, int64_t B,
+                                           const int64_t *__restrict__ slen) {
     // (one shared table copy: 8 or 16 lane-interleaved copies against the gathers' bank
     // conflicts measured no faster, profiles/r04/q1dec/)
     const int64_t G = GC ? GC : Garg;
@@ -1584,6 +1585,14 @@ __global__ LAC_DEC_BOUNDS void k_q1_decode(const LT *__restrict__ lg, int64_t st
     const uint64_t mynbits = rfl_u64(nbits[b]);
     const int64_t nvec = V / N;
     const bool small = SMALL;                                   // (the host passes prec <= 50)
+    // per-stream counts (lac_set_stream_lengths): the stream's live steps of this launch (a
+    // scalar bound), -1 for the rest.  The statistics kernels know no counts: a dead row's
+    // totals are computed (from whatever the row holds) and never read here.
+    if (slen) {
+        const int64_t nall = nsteps;
+        nsteps = live_steps(slen, b, st.nsym, nall);
+        for (int64_t j = nsteps + lane; j < nall; j += 64) sym_out[(t0 + j) * B + b] = -1;
+    }
     uint64_t next = nsteps > 0 ? chunks[b * 64 + lane] : 0;
     float mnext = nsteps > 0 ? mrow[b] : 0.f;
     // (as k_decode_lean) a 32-bit step counter, running row pointers, and the symbols
@@ -2163,12 +2172,12 @@ static int q1_decode(lac_ctx *c, const Q1Args &a0, int64_t steps, int32_t *out, 
 #define LAC_Q1_DEC(GC)                                                                                            \
     k_q1_decode<LT, GC><<<blocks, 64 * kWavesPerBlock, 0, st>>>((const LT *)a.lg, a.ss, a.bs, t0, n, c->V, c->prec, \
                                                                a.xsh, G, c->q1chunks, c->q1m, c->dec, c->dbits,    \
-                                                               c->dstride, c->dnbits, out, c->B)
+                                                               c->dstride, c->dnbits, out, c->B, stream_lengths(c))
         // prec > 50 (quotients past div_small's range): the general form, 128-bit divisions
         if (c->prec > 50)
             k_q1_decode<LT, 0, false><<<blocks, 64 * kWavesPerBlock, 0, st>>>(
                 (const LT *)a.lg, a.ss, a.bs, t0, n, c->V, c->prec, a.xsh, G, c->q1chunks, c->q1m, c->dec, c->dbits,
-                c->dstride, c->dnbits, out, c->B);
+                c->dstride, c->dnbits, out, c->B, stream_lengths(c));
         else switch (G) {
         case 1: LAC_Q1_DEC(1); break;
         case 2: LAC_Q1_DEC(2); break;

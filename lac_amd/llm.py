@@ -295,12 +295,27 @@ class LogitsCompressor:
         return BatchCoder(self.vcode, B, prec=self.prec, pmf_bits=32, capacity_bits=T * (self.prec + 2) + 256,
                           device=self.device)
 
-    def compress(self, tokens):
-        """tokens: int tensor [B, T] -> (list of B byte strings, nbits uint64[B])."""
+    def _lengths(self, lengths, B, T):
+        n = np.asarray(lengths.detach().cpu().numpy() if hasattr(lengths, "detach") else lengths)
+        if n.shape != (B,) or n.dtype.kind not in "iu" or (n.size and (int(n.min()) < 0 or int(n.max()) > T)):
+            raise ValueError(f"lengths: {B} integers in [0, {T}]")
+        return n.astype(np.int64)
+
+    def compress(self, tokens, lengths=None):
+        """tokens: int tensor [B, T] -> (list of B byte strings, nbits uint64[B]).
+        ``lengths`` (B counts in [0, T]): row b is only lengths[b] tokens long -- T stays the
+        padded length; tokens[b, lengths[b]:] are padding, never coded (their values only
+        feed the model, any in-range token does)."""
         import torch
         tokens = tokens.to(self.device, torch.long)
         B, T = tokens.shape
         coder = self._coder(B, T)
+        if lengths is not None:
+            n = self._lengths(lengths, B, T)
+            coder.set_stream_lengths(n)
+            # the padding feeds the model BOS, as decompress does for an ended stream
+            live = torch.arange(T, device=self.device)[None, :] < torch.as_tensor(n, device=self.device)[:, None]
+            tokens = torch.where(live, tokens, torch.full_like(tokens, self.bos))
         if self.incremental:
             sym = tokens.t().contiguous().to(torch.int32)          # [T, B]
             coder.reset()
@@ -313,8 +328,10 @@ class LogitsCompressor:
         coder.close()
         return out
 
-    def decompress(self, data, nbits, T):
-        """Inverse of compress: B byte strings + bit counts -> tokens [B, T] (long)."""
+    def decompress(self, data, nbits, T, lengths=None):
+        """Inverse of compress: B byte strings + bit counts -> tokens [B, T] (long).
+        ``lengths`` as given to compress (T the same padded length): out[b, lengths[b]:] is
+        -1, and an ended stream feeds the model BOS."""
         import torch
         B = len(data)
         stride = max(8, (max((len(d) for d in data), default=0) + 8) // 8 * 8)
@@ -324,10 +341,15 @@ class LogitsCompressor:
         coder = self._coder(B, T)
         bits = torch.from_numpy(buf).to(self.device)
         nb = torch.as_tensor(np.asarray(nbits, dtype=np.int64), device=self.device)
+        if lengths is not None:
+            coder.set_stream_lengths(self._lengths(lengths, B, T))
         coder.decode_open(bits, nb)
         out = torch.empty((B, T), dtype=torch.long, device=self.device)
+        # the token fed back for a decoded -1 (a stream past its count; none without lengths,
+        # where an error raises below): BOS -- the model needs an input, the coder ignores the row
+        fed = (lambda s: torch.where(s < 0, torch.full_like(s, self.bos), s)) if lengths is not None else (lambda s: s)
         if self.incremental:
-            for t, lg in self._steps(B, T, lambda t: out[:, t]):
+            for t, lg in self._steps(B, T, lambda t: fed(out[:, t])):
                 out[:, t] = coder.decode_logits(lg)[0].to(torch.long)
         else:
             ctx = torch.zeros((B, T), dtype=torch.long, device=self.device)
@@ -337,7 +359,7 @@ class LogitsCompressor:
                 s = coder.decode_logits(lg.transpose(0, 1))[0].to(torch.long)
                 out[:, t] = s
                 if t + 1 < T:
-                    ctx[:, t + 1] = s
+                    ctx[:, t + 1] = fed(s)
         coder.raise_on_error()
         coder.close()
         return out
