@@ -322,9 +322,6 @@ __device__ inline uint64_t wave_sum8_u64(const uint64_t (&s)[8], uint32_t &ovf) 
                                    // and the next row's first group over the step's tail (+2.5 %)
 #define LAC_DEC_XPF 1
 #endif
-#ifndef LAC_DEC_STREAM_ONLY        // timing experiment only: skip the search (wrong symbols)
-#define LAC_DEC_STREAM_ONLY 0
-#endif
 
 // k_decode_wave with one total per 64-vector iteration of the row instead of per
 // <= 64-iteration chunk (rows of <= 512 iterations: V <= 131072 u32 / 65536 u64
@@ -488,8 +485,7 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
                 }
                 return false;
             };
-            if (LAC_DEC_STREAM_ONLY) s = (int64_t)(minp & 1);
-            else err = decode_symbol<E, VEC>(st, row, V, T, minp, prec, mapping, mybits, mynbits, find_chunk, &s);
+            err = decode_symbol<E, VEC>(st, row, V, T, minp, prec, mapping, mybits, mynbits, find_chunk, &s);
         }
         if (err) {
             st.err = err;
@@ -678,21 +674,8 @@ __device__ inline void dec_chunk_layout(int64_t V, int64_t *CI, int64_t *nch) {
     *nch = (nit + ci - 1) / ci;
 }
 
-// The lean step's chunks: up to 64 * LeanCW<E> of them, LeanCW bounds per lane -- u64 rows
-// two (V = 32000: 125 chunks of 2 iterations, two 16-B loads per lane and step instead of
-// four), u32 rows one (the layout above).
-#ifndef LAC_LEAN_CW32
-#define LAC_LEAN_CW32 1          // (2 for u32 rows too: c2 0.849-0.851 vs 0.848-0.850 us, profiles/r06/lean3/cw32/)
-#endif
-template <typename E> constexpr int LeanCW = sizeof(E) == 8 ? 2 : LAC_LEAN_CW32;
+// (the lean step's chunks, up to 64 * LeanCW<E> of them: lean_chunk_layout, lac_select.h)
 typedef VecT<uint64_t, 2>::type u64x2;
-template <typename E, int VEC>
-__host__ __device__ inline void lean_chunk_layout(int64_t V, int64_t *CI, int64_t *nch) {
-    const int64_t nvec = V / VEC, nit = (nvec + 63) / 64, per = 64 * LeanCW<E>;
-    const int64_t ci = nit ? (nit + per - 1) / per : 1;
-    *CI = ci;
-    *nch = (nit + ci - 1) / ci;
-}
 
 // What k_decode_lean reads of a row (LEAN builds of k_dec_stats), besides its CDF:
 struct LeanMeta {
@@ -981,32 +964,12 @@ __global__ __launch_bounds__(256) void k_decode_seq(const E *__restrict__ pmf, i
 #ifndef LAC_LEAN_AHEAD
 #define LAC_LEAN_AHEAD 16
 #endif
-#ifndef LAC_LEAN_HELPERS
-#define LAC_LEAN_HELPERS 16
-#endif
 constexpr int kLeanAhead = LAC_LEAN_AHEAD;      // rows prefetched ahead of the decoder
-constexpr int kLeanHelpers = LAC_LEAN_HELPERS;  // helper waves per stream
-// Up to 44 streams: the stats pass of the lean step writes a full CDF copy of every row, so
-// its per-step cost grows with the streams, and k_decode_seq's read-only pass overtakes it
-// between 32 and 64 (V=32000 u32, decode us per step lean / seq: 8 streams 1.17 / 2.75,
-// 16 1.76 / 2.90, 32 2.75 / 3.25, 64 4.52 / 3.91; profiles/r06/lean3/fewstreams/)
-#ifndef LAC_LEAN_MAX_STREAMS
-#define LAC_LEAN_MAX_STREAMS 44
-#endif
-constexpr int64_t kLeanMaxStreams = LAC_LEAN_MAX_STREAMS;   // k_decode_lean up to this many streams
-constexpr int kLeanHelpMaxStreams = 16;         // above: no helpers (L2: ~2.6 MB ahead per stream)
 #ifndef LAC_LEAN_PUB
 #define LAC_LEAN_PUB 8
 #endif
 constexpr int kLeanPub = LAC_LEAN_PUB;          // the decoder publishes its progress every kLeanPub steps
-#ifndef LAC_LEAN_BYTES
-#define LAC_LEAN_BYTES (512ll << 20)   // (256 MB: c2 u64 1.47 us per step, 512 MB 1.44: more stats waves per CU)
-#endif
-constexpr int64_t kLeanBytes = LAC_LEAN_BYTES;  // CDF rows per launch: at most this many bytes
-#ifndef LAC_LEAN_ROUNDS
-#define LAC_LEAN_ROUNDS 3
-#endif
-constexpr int kLeanRounds = LAC_LEAN_ROUNDS;    // k_decode_seq one step + lean again, per launch group
+// (kLeanHelpers, kLeanMaxStreams, kLeanHelpMaxStreams, kLeanBytes, kLeanRounds: lac_select.h)
 #ifndef LAC_LEAN_WIDE_WINDOW
 #define LAC_LEAN_WIDE_WINDOW 1                  // wide u64 rows: the search against a double window
 #endif
@@ -1427,47 +1390,53 @@ __global__ __launch_bounds__(64) void k_decode_lean(const E *__restrict__ lcdf, 
 
 }  // namespace
 
+// Which kernels decode a call is decode_plan's choice (lac_select.h); the launchers below
+// take the plan, keep the buffers and launch.
+static_assert(kWavesPerBlock == 4, "decode_plan's step_waves");
+// (what k_decode_step, k_decode_wave(_fine) and k_decode_block take after the table and its strides)
+#define LAC_DEC_ARGS \
+    c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B, c->mapping, stream_lengths(c)
+
 template <typename E, int VEC, int G>
-static int decode_launch(lac_ctx *c, const E *pmf, int64_t step_off, int64_t stream_stride, int32_t *out,
-                         hipStream_t st) {
+static int decode_launch(lac_ctx *c, const DecodePlan &p, const E *pmf, int64_t step_off, int64_t stream_stride,
+                         int32_t *out, hipStream_t st) {
     constexpr int64_t CH = 64 * VEC * G;
-    const int64_t nch = (c->V + CH - 1) / CH;
-    const size_t lds = sizeof(uint64_t) * (size_t)nch;
-    if (lds > 64 * 1024) return fail(LAC_E_ARG, "vocab too large for the decode chunk table");
+    const size_t lds = sizeof(uint64_t) * (size_t)((c->V + CH - 1) / CH);   // (<= 64 KB: decode_plan)
     ProfScope ps(c, KID_DECODE, st);
-    if (c->B <= 256)        // few streams: 16 waves per stream keep the whole row in flight
-        k_decode_step<E, VEC, G, 16><<<(unsigned)c->B, 64 * 16, lds, st>>>(
-            pmf, step_off, stream_stride, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping, stream_lengths(c));
+    if (p.step_waves == 16)
+        k_decode_step<E, VEC, G, 16><<<(unsigned)c->B, 64 * 16, lds, st>>>(pmf, step_off, stream_stride, LAC_DEC_ARGS);
     else
         k_decode_step<E, VEC, G, kWavesPerBlock><<<(unsigned)c->B, 64 * kWavesPerBlock, lds, st>>>(
-            pmf, step_off, stream_stride, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping, stream_lengths(c));
+            pmf, step_off, stream_stride, LAC_DEC_ARGS);
     CHECK_LAUNCH();
     return LAC_OK;
 }
 
+// The whole call in one launch: a wave per stream (k_decode_wave, or _fine with NR
+// registers of per-iteration totals) or a workgroup of NW waves per stream (k_decode_block).
 template <typename E, int VEC>
-static int decode_wave_launch(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t stream_stride, int64_t steps,
-                              int32_t *out, hipStream_t st) {
+static int decode_call_launch(lac_ctx *c, const DecodePlan &p, const E *pmf, int64_t step_stride,
+                              int64_t stream_stride, int64_t steps, int32_t *out, hipStream_t st) {
     ProfScope ps(c, KID_DECODE_WAVE, st);
     const unsigned blocks = (unsigned)((c->B + kStreamWaves - 1) / kStreamWaves);
-    const int64_t nit = (c->V / VEC + 63) / 64;               // 64-vector iterations per row
-#define LAC_FINE(NR)                                                                                              \
-    k_decode_wave_fine<E, VEC, NR><<<blocks, 64 * kStreamWaves, 0, st>>>(                                        \
-        pmf, step_stride, stream_stride, steps, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B, \
-        c->mapping, stream_lengths(c))
-    bool fine = false;
-    if constexpr (VEC > 1) {
-        fine = c->fine_decode && nit <= 512;
-        if (fine && nit <= 128) LAC_FINE(2);
-        else if (fine && nit <= 256) LAC_FINE(4);
-        else if (fine) LAC_FINE(8);
+#define LAC_FINE(NR)                                                     \
+    k_decode_wave_fine<E, VEC, NR><<<blocks, 64 * kStreamWaves, 0, st>>>( \
+        pmf, step_stride, stream_stride, steps, LAC_DEC_ARGS)
+#define LAC_BLK(NW) \
+    k_decode_block<E, VEC, NW><<<(unsigned)c->B, 64 * NW, 0, st>>>(pmf, step_stride, stream_stride, steps, LAC_DEC_ARGS)
+    const int nr = VEC > 1 && p.path == DEC_WAVE ? p.fine_nr : 0;
+    if constexpr (VEC > 1) {                                    // (vector rows only)
+        if (p.path == DEC_BLOCK && p.block_nw == 4) LAC_BLK(4);
+        else if (p.path == DEC_BLOCK && p.block_nw == 8) LAC_BLK(8);
+        else if (p.path == DEC_BLOCK) LAC_BLK(16);
+        else if (nr == 2) LAC_FINE(2);
+        else if (nr == 4) LAC_FINE(4);
+        else if (nr) LAC_FINE(8);
     }
-    if (!fine)
-        k_decode_wave<E, VEC><<<blocks, 64 * kStreamWaves, 0, st>>>(
-            pmf, step_stride, stream_stride, steps, c->V, c->prec, c->dec, c->dbits, c->dstride, c->dnbits, out, c->B,
-            c->mapping, stream_lengths(c));
+    if (p.path == DEC_WAVE && !nr)
+        k_decode_wave<E, VEC><<<blocks, 64 * kStreamWaves, 0, st>>>(pmf, step_stride, stream_stride, steps,
+                                                                     LAC_DEC_ARGS);
+#undef LAC_BLK
 #undef LAC_FINE
     CHECK_LAUNCH();
     return LAC_OK;
@@ -1481,41 +1450,16 @@ int ensure_chunk_buffers(lac_ctx *c) {
 }
 
 template <typename E, int VEC>
-static int decode_stats_path(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t stream_stride, int64_t steps,
-                             int32_t *out, hipStream_t st) {
+static int decode_stats_path(lac_ctx *c, const DecodePlan &p, const E *pmf, int64_t step_stride,
+                             int64_t stream_stride, int64_t steps, int32_t *out, hipStream_t st) {
     int rc = ensure_chunk_buffers(c);
     if (rc) return rc;
     const unsigned blocks = (unsigned)((c->B + kWavesPerBlock - 1) / kWavesPerBlock);
-    // A static model (stride-0 steps): every step reads the same row per stream, so the
-    // statistics are computed once per stream (rstep 0) and one launch pair covers any
-    // number of steps.
-    const bool stat = step_stride == 0;
-    const int64_t rstep = stat ? 0 : c->B;
-    // k_decode_lean: prec <= 50, chunks of at most 4 iterations (V <= 65536 entries: 64 chunk
-    // bounds per u32 row, 128 per u64 row), totals lean_total_ok<E> (checked per row); its
-    // CDF buffer holds up to kLeanBytes, so a launch takes at most that many steps' rows
-    const int64_t nvec = c->V / VEC;
-    int64_t CI, lnch;
-    lean_chunk_layout<E, VEC>(c->V, &CI, &lnch);
-    // Only for the fewest streams: the stats pass writes as many bytes more as it reads (the
-    // CDF), which costs more than the shorter chain saves once enough streams run side by
-    // side (round 4, per-vector CDF, V=32000: B=4 1.36 vs 2.66 us/step, 64 3.41 vs 3.96, 128
-    // 5.39 vs 5.26; profiles/r04/lean/fewstreams/)
+    // (a static model's statistics: one row per stream, rstep 0)
+    const bool stat = p.static_rows, lean = p.lean, help = p.help;
+    const int64_t rstep = stat ? 0 : c->B, cs = p.cs, CI = p.CI;
     const int64_t wstride = (int64_t)(c->dstride / 8) + 2;     // k_lean_window's words per stream
-    bool lean = false;
-    // Per-stream counts (lac_set_stream_lengths) take k_decode_seq, as LAC_OPT_DECODE_STOP takes
-    // this path: the lean step and its prefetching helpers stay unaware of counts, so no
-    // helper waits on a decoder that has left at its count.
-    if constexpr (VEC > 1)
-        lean = LAC_LEAN && c->prec <= 50 && CI <= 4 && nvec > 0 && c->B <= kLeanMaxStreams && !c->has_len;
-    int64_t cs = stat ? steps : c->chunk_steps;
     if (lean) {
-        const int64_t rows_fit = kLeanBytes / (c->V * (int64_t)sizeof(E));
-        if (!stat) {
-            const int64_t fit = rows_fit / c->B;
-            const int64_t ls = fit < 64 ? 64 : fit / 64 * 64;
-            cs = ls < cs ? ls : cs;
-        }
         const int64_t need = stat ? c->B : cs * c->B;          // CDF rows per launch
         if (c->lean_rows < need || c->lean_esize != (int)sizeof(E)) {
             (void)hipFree(c->lcdf);
@@ -1546,9 +1490,7 @@ static int decode_stats_path(lac_ctx *c, const E *pmf, int64_t step_stride, int6
                                                                      c->B);
         CHECK_LAUNCH();
     }
-    // prefetching helper workgroups for the fewest streams (kLeanHelpers per stream, dealt
-    // to the stream's XCD); a static model's rows stay in L2 without them
-    const bool help = lean && !stat && LAC_LEAN_HELP && c->B <= kLeanHelpMaxStreams;
+    // the helpers' workgroups: kLeanHelpers per stream, dealt to the stream's XCD
     const int64_t B8 = (c->B + 7) & ~(int64_t)7;
     const unsigned lean_blocks = (unsigned)(help ? B8 * (1 + kLeanHelpers) : c->B);
     if (help && !c->dprogress) HIPCHK(hipMalloc(&c->dprogress, sizeof(int32_t) * c->B));
@@ -1612,76 +1554,40 @@ static int decode_stats_path(lac_ctx *c, const E *pmf, int64_t step_stride, int6
     return LAC_OK;
 }
 
-template <typename E, int VEC>
-static int decode_block_launch(lac_ctx *c, const E *pmf, int64_t step_stride, int64_t stream_stride, int64_t steps,
-                               int32_t *out, hipStream_t st) {
-    ProfScope ps(c, KID_DECODE_WAVE, st);
-    const int nw = c->block_waves ? c->block_waves : (c->B >= 1024 ? 4 : c->B >= 512 ? 8 : 16);
-#define LAC_BLK(NW)                                                                                              \
-    k_decode_block<E, VEC, NW><<<(unsigned)c->B, 64 * NW, 0, st>>>(pmf, step_stride, stream_stride, steps, c->V,  \
-                                                                  c->prec, c->dec, c->dbits, c->dstride, c->dnbits, \
-                                                                  out, c->B, c->mapping, stream_lengths(c))
-    if (nw == 4) LAC_BLK(4);
-    else if (nw == 8) LAC_BLK(8);
-    else LAC_BLK(16);
-#undef LAC_BLK
-    CHECK_LAUNCH();
-    return LAC_OK;
+// f(ElemVec<E, VEC>) for the table's entry type and the plan's vector width (4 u32 / 2 u64, or 1)
+template <typename E_, int VEC_>
+struct ElemVec {
+    typedef E_ E;
+    static constexpr int VEC = VEC_;
+};
+template <typename F>
+static int with_elem_vec(int pmf_bits, int vec, F f) {
+    if (pmf_bits == 32) return vec > 1 ? f(ElemVec<uint32_t, 4>()) : f(ElemVec<uint32_t, 1>());
+    return vec > 1 ? f(ElemVec<uint64_t, 2>()) : f(ElemVec<uint64_t, 1>());
 }
 
 static int decode_dispatch(lac_ctx *c, const void *pmf, int64_t step_stride, int64_t stream_stride, int64_t steps,
                            int32_t *out, hipStream_t st) {
-    const uintptr_t p = (uintptr_t)pmf;
-    if (c->dec_stop) {                      // LAC_OPT_DECODE_STOP: the stats path's kernels implement it
-        if (c->pmf_bits == 32)
-            return (p % 16 == 0) && c->V % 4 == 0 && step_stride % 4 == 0 && stream_stride % 4 == 0
-                       ? decode_stats_path<uint32_t, 4>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st)
-                       : decode_stats_path<uint32_t, 1>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st);
-        return (p % 16 == 0) && c->V % 2 == 0 && step_stride % 2 == 0 && stream_stride % 2 == 0
-                   ? decode_stats_path<uint64_t, 2>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st)
-                   : decode_stats_path<uint64_t, 1>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st);
-    }
-    const bool wave = c->dpath == LAC_PATH_FUSED || (c->dpath == LAC_PATH_AUTO && c->B >= c->wave_decode_min_streams);
-    const int vw = c->pmf_bits == 32 ? 4 : 2;
-    const bool vec = (p % 16 == 0) && c->V % vw == 0 && step_stride % vw == 0 && stream_stride % vw == 0;
-    const bool blockable = vec && (c->V / vw + 63) / 64 <= 512;        // per-iteration totals fit LDS
-    if (blockable && (c->dpath == LAC_PATH_BLOCK || (c->dpath == LAC_PATH_AUTO && !wave &&
-                                                     ((c->B >= c->block_window_lo && c->B <= c->block_window_hi) ||
-                                                      c->B >= c->block_decode_min_streams)))) {
-        if (c->pmf_bits == 32)
-            return decode_block_launch<uint32_t, 4>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st);
-        return decode_block_launch<uint64_t, 2>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st);
-    }
-    if (c->dpath == LAC_PATH_STATS || c->dpath == LAC_PATH_BLOCK || (c->dpath == LAC_PATH_AUTO && !wave)) {
-        if (c->pmf_bits == 32)
-            return vec ? decode_stats_path<uint32_t, 4>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st)
-                       : decode_stats_path<uint32_t, 1>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st);
-        return vec ? decode_stats_path<uint64_t, 2>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st)
-                   : decode_stats_path<uint64_t, 1>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st);
-    }
-    if (wave) {
-        if (c->pmf_bits == 32)
-            return vec ? decode_wave_launch<uint32_t, 4>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st)
-                       : decode_wave_launch<uint32_t, 1>(c, (const uint32_t *)pmf, step_stride, stream_stride, steps, out, st);
-        return vec ? decode_wave_launch<uint64_t, 2>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st)
-                   : decode_wave_launch<uint64_t, 1>(c, (const uint64_t *)pmf, step_stride, stream_stride, steps, out, st);
-    }
-    for (int64_t t = 0; t < steps; t++) {
-        const int64_t off = t * step_stride;
-        int32_t *o = out + t * c->B;
-        int rc;
-        const bool few = c->B <= 256;                         // 16-wave workgroups: 8 loads/lane per chunk
-        if (c->pmf_bits == 32)
-            rc = vec ? (few ? decode_launch<uint32_t, 4, 8>(c, (const uint32_t *)pmf, off, stream_stride, o, st)
-                            : decode_launch<uint32_t, 4, 2>(c, (const uint32_t *)pmf, off, stream_stride, o, st))
-                     : decode_launch<uint32_t, 1, 8>(c, (const uint32_t *)pmf, off, stream_stride, o, st);
-        else
-            rc = vec ? (few ? decode_launch<uint64_t, 2, 8>(c, (const uint64_t *)pmf, off, stream_stride, o, st)
-                            : decode_launch<uint64_t, 2, 4>(c, (const uint64_t *)pmf, off, stream_stride, o, st))
-                     : decode_launch<uint64_t, 1, 8>(c, (const uint64_t *)pmf, off, stream_stride, o, st);
-        if (rc) return rc;
-    }
-    return LAC_OK;
+    const DecodeKnobs k{c->dpath, c->wave_decode_min_streams, c->block_decode_min_streams, c->block_window_lo,
+                        c->block_window_hi, c->block_waves, c->fine_decode, c->dec_stop, c->has_len, c->chunk_steps};
+    const DecodePlan p = decode_plan(k, c->B, c->V, c->pmf_bits, c->prec, (uintptr_t)pmf % 16 == 0, step_stride,
+                                     stream_stride, steps);
+    if (p.rc) return fail(p.rc, "vocab too large for the decode chunk table");
+    return with_elem_vec(c->pmf_bits, p.vec, [&](auto ev) {
+        typedef typename decltype(ev)::E E;
+        constexpr int VEC = decltype(ev)::VEC;
+        const E *tab = (const E *)pmf;
+        if (p.path == DEC_STATS) return decode_stats_path<E, VEC>(c, p, tab, step_stride, stream_stride, steps, out, st);
+        if (p.path != DEC_PER_STEP)
+            return decode_call_launch<E, VEC>(c, p, tab, step_stride, stream_stride, steps, out, st);
+        constexpr int GM = VEC == 1 ? 8 : sizeof(E) == 4 ? 2 : 4;   // vector rows, many streams: fewer loads per lane
+        for (int64_t t = 0; t < steps; t++) {
+            const int rc = p.G == 8 ? decode_launch<E, VEC, 8>(c, p, tab, t * step_stride, stream_stride, out + t * c->B, st)
+                                    : decode_launch<E, VEC, GM>(c, p, tab, t * step_stride, stream_stride, out + t * c->B, st);
+            if (rc) return rc;
+        }
+        return (int)LAC_OK;
+    });
 }
 
 

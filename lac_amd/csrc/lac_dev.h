@@ -39,12 +39,6 @@ using namespace lac;
 #ifndef LAC_UNROLL
 #define LAC_UNROLL 8
 #endif
-#ifndef LAC_LEAN
-#define LAC_LEAN 1          // few-stream decode: k_decode_lean ahead of k_decode_seq (probe builds set 0)
-#endif
-#ifndef LAC_LEAN_HELP
-#define LAC_LEAN_HELP 1     // k_decode_lean: L2-prefetching helper workgroups for <= 16 streams
-#endif
 #ifndef LAC_NT
 #define LAC_NT 1
 #endif

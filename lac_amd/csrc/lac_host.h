@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "lac_dev.h"
+#include "lac_select.h"
 
 // ====================================================================== C-ABI
 struct lac_ctx {
@@ -60,7 +61,8 @@ struct lac_ctx {
     uint64_t *lwin = nullptr;           //              [B][lwin_stride] the bit streams as big-endian words, zero-padded
     int64_t lwin_words = 0;             //              words lwin holds
     float *q1m = nullptr;               //                [chunk_steps * B] row maxima
-    uint64_t *pxch = nullptr;           // paired row stats (shape 19): [2 * cus] maximum words
+    uint64_t *pxch = nullptr;           // row-group stats (shapes 19..21, 23): [8 * cus + 1] words -- a pair of
+                                        // maximum words per row slot (<= 4 per CU), then the abort word
     int64_t xch_abort = -1;             // word of pxch holding the last row-group launch's abort flag
     int64_t *slen = nullptr;            // lac_set_stream_lengths: [B] per-stream symbol counts (the context's copy)
     bool has_len = false;               //                         counts are set (kernels get slen, else nullptr)
@@ -142,5 +144,3 @@ int enc_finish_launch(lac_ctx *c, int term, hipStream_t st);
 // decode family (lac_decode.hip): the per-chunk-of-steps buffers the stats path and the
 // logits decode share
 int ensure_chunk_buffers(lac_ctx *c);
-// logits family (lac_logits.hip): whether a q1 row-stats shape exists (lac_set_option)
-bool q1_shape_live(int sh);

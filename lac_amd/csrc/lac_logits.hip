@@ -645,9 +645,7 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
 // vectors (bf16 V <= 128512: Llama-3's 128256) need only LASTN = 704 threads' worth
 // of the last slot, which leaves room for 16 copies (two lanes per copy).
 // Same outputs as k_q1_stats (RowStats, or row max + 64 chunk totals).
-constexpr int kRLRep = 8;
-constexpr int kRLLastTrim = 704;                 // last-slot threads of the 16-copy form
-constexpr int kRLTrimMaxVec = 15 * 1024 + kRLLastTrim;   // rows it holds: 16064 vectors
+// (kRLRep, kRLLastTrim, kRLTrimMaxVec: lac_select.h)
 typedef __attribute__((address_space(3))) void lvoid_t;
 
 // NT < 1024: 1024 / NT rows per block, NT threads (NT / 64 waves) each, for
@@ -685,9 +683,6 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 // previous row's epilogue between the post and the poll (ab_late) nor per-row LDS
 // barriers with odd rows started half a round late, so that other rows stream while
 // one waits (ab_rowbar, ab_rbo), recovered any of it.
-#ifndef LAC_Q1_GROUP_NOWAIT
-#define LAC_Q1_GROUP_NOWAIT 0
-#endif
 constexpr uint32_t kGroupSpinMax = 1u << 17;                 // polls (s_sleep 2 + a device-scope load each): ~0.1 s,
                                                              // far beyond any wait for a resident partner
 
@@ -713,7 +708,7 @@ __device__ inline uint64_t group_ld(const uint64_t *p) {
 // whose partner did not post within kGroupSpinMax polls -- not resident, e.g.
 // while another kernel holds CUs -- sets it; every block then stops waiting at
 // once (its rows are poisoned) and the gated tiled launch queued behind this one
-// (q1_group_kernel) recomputes every row without row groups.
+// (q1_group_repair) recomputes every row without row groups.
 // Posting (group_post: one lane) and polling (group_poll: a whole wave, the row's
 // first: lane k < kg polls partner slot q0 + k, so the kg - 1 words' L2 round trips
 // overlap instead of queueing one after another; the lanes' values are folded with
@@ -729,10 +724,6 @@ __device__ inline uint32_t group_poll(uint64_t *xch, uint64_t *abortw, int g, in
                                       Op op, bool *ok) {
     const unsigned b = blockIdx.x, sl = seq & 1, xcd = b & 7, q = (b >> 3) * NRB + g, q0 = (q / kg) * kg;
     const unsigned lane = (unsigned)lane_fresh();
-#if LAC_Q1_GROUP_NOWAIT                                          // timing experiment only: wrong tables
-    *ok = true;
-    return m;
-#endif
     const unsigned pq = q0 + lane;
     uint32_t val = m;                                            // lanes without a partner hold the neutral m
     bool fine = true;
@@ -1541,10 +1532,6 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
         asm volatile("" ::: "memory");
     }
 }
-constexpr int kQ1WideR = 40;
-constexpr int kQ1WideMaxVec = 512 * kQ1WideR;                  // registers only
-constexpr int kQ1WideL = 11;                                   // + LDS slots (the 32-copy table beside them)
-constexpr int kQ1WideSlotMaxVec = 512 * (kQ1WideR + kQ1WideL);
 
 // k_q1_decode: one wave per stream, sequential over a chunk of steps, from the
 // chunk totals of k_q1_stats: per step it finds the chunk holding
@@ -1793,11 +1780,6 @@ static int logits_check(lac_ctx *c, const void *lg, int type, int64_t step_strid
     return LAC_OK;
 }
 
-static int64_t q1_groups_per_chunk(int64_t nvec) {                // 64-vector groups per decode chunk
-    const int64_t groups = (nvec + 63) / 64;
-    return groups <= 64 ? 1 : (groups + 63) / 64;
-}
-
 struct Q1Args {
     const void *lg;
     int64_t ss, bs;
@@ -1806,336 +1788,124 @@ struct Q1Args {
     uint32_t xsh;
 };
 
-template <typename LT, int RW, int R, bool DEC, bool MULTI, bool PF, int NWB = kQ1Waves>
-static int q1_stats_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, const uint64_t *gate = nullptr) {
-    static int per_cu = 0;                                       // resident blocks per CU (occupancy API)
-    if (!per_cu) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_q1_stats<LT, RW, R, DEC, MULTI, PF, NWB>, 64 * NWB,
-                                                         0) != hipSuccess ||
-            n < 1)
-            n = 1;
-        per_cu = n;
-    }
-    constexpr int NR = NWB / RW;
-    const int64_t need = (a.rows + NR - 1) / NR, cap = (int64_t)c->cus * per_cu;
-    const unsigned grid = (unsigned)(need < cap ? need : cap);
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    ProfScope ps(c, gate ? -1 : KID_Q1_STATS, st);            // (a gated repair launch is not profiled)
-    k_q1_stats<LT, RW, R, DEC, MULTI, PF, NWB><<<grid, 64 * NWB, 0, st>>>(
-        (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-        c->q1chunks, c->q1m, gate);
-    CHECK_LAUNCH();
-    return LAC_OK;
-}
+// Which kernel runs is q1_plan's choice (lac_select.h); the launchers below map a plan to
+// its template instance and compute the grid.  What every row-statistics kernel starts with:
+#define LAC_Q1_ARGS                                                                                            \
+    (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, p.groups_per_chunk, c->stats, c->q1chunks, \
+        c->q1m
 
-template <typename LT, bool DEC>
-static int q1_wide_launch(lac_ctx *c, const Q1Args &a, hipStream_t st) {
-    const int64_t cap = (int64_t)c->cus;                         // one 8-wave block per CU
-    const unsigned grid = (unsigned)(a.rows < cap ? a.rows : cap);
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    ProfScope ps(c, KID_Q1_STATS, st);
-    if (nvec <= kQ1WideMaxVec)
-        k_q1_stats_wide<LT, kQ1WideR, DEC><<<grid, 512, 0, st>>>(
-            (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-            c->q1chunks, c->q1m, nullptr, 0, 1, 0);
-    else                                                         // rows past the registers: + LDS slots
-        k_q1_stats_wide<LT, kQ1WideR, DEC, false, kQ1WideL><<<grid, 512, 0, st>>>(
-            (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-            c->q1chunks, c->q1m, nullptr, 0, 1, 0);
-    CHECK_LAUNCH();
-    return LAC_OK;
-}
-
-template <typename LT, bool DEC, int REP, int LASTN, int NT>
-static int q1_rl_kernel(lac_ctx *c, const Q1Args &a, hipStream_t st) {
-    constexpr int NRB = 1024 / NT;
-    const int64_t need = (a.rows + NRB - 1) / NRB, cap = (int64_t)c->cus;   // one 16-wave block per CU
-    const unsigned grid = (unsigned)(need < cap ? need : cap);
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    ProfScope ps(c, KID_Q1_STATS, st);
-    k_q1_stats_rl<LT, DEC, REP, LASTN, NT><<<grid, 1024, 0, st>>>(
-        (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-        c->q1chunks, c->q1m, nullptr, 0, 1, 0);
-    CHECK_LAUNCH();
-    return LAC_OK;
-}
-
-// Grouped row stats (shapes 19 / 20 / 21): a row in kg segments of `split` vectors
-// (a multiple of 64; the last one the rest), one per row slot of the rl kernel
-// with NRB = 1 / 2 / 4 rows per block; every segment must fit its slot -- the
-// 16-copy form (16064 / 8000 / 4032 vectors) or the 8-copy form (16384 / 8192 /
-// 4096).  Decode has no 16-copy form at NRB = 4 (LDS: its group totals).
-constexpr int kQ1MaxSeg = 16;                    // segments per row (lanes polling partners)
-struct Q1Group {
-    int k = 0, split = 0, nrb = 1;
-    bool rep16 = false;
-    double score = 0;
-};
-static int64_t q1_slot_cap(int nrb, bool rep16) {
-    if (nrb == 1) return rep16 ? kRLTrimMaxVec : 16384;
-    if (nrb == 2) return rep16 ? 15 * 512 + 320 : 8192;
-    return rep16 ? 15 * 256 + 192 : 4096;
-}
-// the fewest segments of this form; score = the row's share of its slots' capacity
-// (the bytes a CU keeps in flight) x the share of the XCD's slots in use
-static bool q1_group_form(lac_ctx *c, int64_t nvec, int nrb, bool rep16, Q1Group *g) {
-    const int64_t ngrp = (nvec + 63) / 64, lim = q1_slot_cap(nrb, rep16), spx = (int64_t)(c->cus / 8) * nrb;
-    for (int k = 2; k <= kQ1MaxSeg && k <= spx; k++) {
-        const int64_t sp = 64 * ((ngrp + k - 1) / k), last = nvec - (k - 1) * sp;
-        if (last > 0 && sp <= lim && last <= lim) {
-            g->k = k;
-            g->split = (int)sp;
-            g->nrb = nrb;
-            g->rep16 = rep16;
-            g->score = (double)nvec / (k * (16384.0 / nrb)) * (double)((spx / k) * k) / (double)spx;
-            return true;
+// k_q1_stats in the plan's tiled form kQ1Tiled[p.tiled] (instance I: the one tried) -- of a
+// row-group plan its repair, gated on the abort word
+template <typename LT, bool DEC, int I = 0>
+static int q1_tiled_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Plan &p,
+                           const uint64_t *gate = nullptr) {
+    if constexpr (I == kQ1TiledForms) {
+        return fail(LAC_E_ARG, "q1 shape %d has no tiled form", p.shape);
+    } else {
+        if (p.tiled != I) return q1_tiled_launch<LT, DEC, I + 1>(c, a, st, p, gate);
+        constexpr int RW = kQ1Tiled[I][1], R = kQ1Tiled[I][2], NWB = kQ1Tiled[I][5];
+        constexpr bool MULTI = kQ1Tiled[I][3] != 0, PF = kQ1Tiled[I][4] != 0;
+        static_assert(NWB == 16 || NWB == kQ1Waves, "kQ1Tiled's block sizes");
+        static int per_cu = 0;                                   // resident blocks per CU (occupancy API)
+        if (!per_cu) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_q1_stats<LT, RW, R, DEC, MULTI, PF, NWB>, 64 * NWB,
+                                                             0) != hipSuccess ||
+                n < 1)
+                n = 1;
+            per_cu = n;
         }
+        constexpr int NR = NWB / RW;
+        const int64_t need = (a.rows + NR - 1) / NR, cap = (int64_t)c->cus * per_cu;
+        const unsigned grid = (unsigned)(need < cap ? need : cap);
+        ProfScope ps(c, gate ? -1 : KID_Q1_STATS, st);        // (a gated repair launch is not profiled)
+        k_q1_stats<LT, RW, R, DEC, MULTI, PF, NWB><<<grid, 64 * NWB, 0, st>>>(LAC_Q1_ARGS, gate);
+        CHECK_LAUNCH();
+        return LAC_OK;
     }
-    return false;
-}
-// nrb = 0: the best-scoring form (ties: the first, i.e. fewer rows per block and the
-// 16-copy form); decode's 8-copy forms score 5 % lower (q1_rl_rep16: its lookups
-// are the bound there; encode measured the same either way), and bf16 encode's
-// 25 % lower: with the group logic they spill 29-32 VGPRs at the 128 cap (the
-// 16-copy ones none), and the round-2 pair form at V = 262144 ran at 59 % of peak
-// against 78 % for V = 256000's 16-copy halves
-static bool q1_group(lac_ctx *c, int64_t nvec, bool dec, bool bf16, int nrb, Q1Group *best) {
-    bool any = false;
-    for (int n : {1, 2, 4}) {
-        if (nrb && n != nrb) continue;
-        for (int rep16 = 1; rep16 >= 0; rep16--) {
-            if (dec && n == 4 && rep16) continue;
-            Q1Group g;
-            if (!q1_group_form(c, nvec, n, rep16 != 0, &g)) continue;
-            if (!rep16) g.score *= dec ? 0.95 : bf16 ? 0.75 : 1.0;
-            if (!any || g.score > best->score + 1e-9) *best = g;
-            any = true;
-        }
-    }
-    return any;
 }
 
-template <typename LT, bool DEC, int REP, int LASTN, int NT>
-static int q1_group_kernel(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Group &g) {
-    constexpr int NRB = 1024 / NT;
-    const int64_t nvec = c->V / LogitN<LT>::N;
+// Row groups (shapes 19..21: segments in k_q1_stats_rl's row slots, nrb per block; 23: one
+// 8-wave block per segment, nrb = 1): the exchange buffer, the zeroed outputs, the grid.
+static int q1_group_setup(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Group &g, bool dec, unsigned *grid,
+                          int *rpx_out) {
     // (<= 4 rows per block) + the abort word
     if (!c->pxch) HIPCHK(hipMalloc(&c->pxch, sizeof(uint64_t) * (8 * (int64_t)c->cus + 1)));
     // rpx rows per XCD per round (all of the XCD's slots' worth, or all rows in one
     // round), on the fewest blocks that hold rpx * k slots; never more blocks than
     // CUs (one per CU: every partner resident at once)
-    const int64_t spx = (int64_t)(c->cus / 8) * NRB, rcap = spx / g.k, rneed = (a.rows + 7) / 8;
+    const int64_t spx = (int64_t)(c->cus / 8) * g.nrb, rcap = spx / g.k, rneed = (a.rows + 7) / 8;
     const int64_t rpx = rneed < rcap ? rneed : rcap;
-    const unsigned grid = (unsigned)(8 * ((rpx * g.k + NRB - 1) / NRB));
-    HIPCHK(hipMemsetAsync(c->pxch, 0, sizeof(uint64_t) * (2 * NRB * grid + 1), st));   // no stale sequence numbers,
-                                                                                      // abort word clear
+    *grid = (unsigned)(8 * ((rpx * g.k + g.nrb - 1) / g.nrb));
+    *rpx_out = (int)rpx;
+    // no stale sequence numbers, abort word clear
+    HIPCHK(hipMemsetAsync(c->pxch, 0, sizeof(uint64_t) * (2 * g.nrb * (int64_t)*grid + 1), st));
     // the segments add into zeroed outputs
-    if (DEC) HIPCHK(hipMemsetAsync(c->q1chunks, 0, sizeof(uint64_t) * 64 * a.rows, st));
+    if (dec) HIPCHK(hipMemsetAsync(c->q1chunks, 0, sizeof(uint64_t) * 64 * a.rows, st));
     else HIPCHK(hipMemsetAsync(c->stats, 0, sizeof(RowStats) * a.rows, st));
+    return LAC_OK;
+}
+
+// repair: the tiled two-pass shape over the same rows, gated on the abort word
+// (its blocks exit at once when the groups completed: one small launch per job)
+template <typename LT, bool DEC>
+static int q1_group_repair(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Plan &p, unsigned grid) {
+    c->xch_abort = 2 * p.group.nrb * (int64_t)grid;
+    return q1_tiled_launch<LT, DEC>(c, a, st, p, c->pxch + c->xch_abort);
+}
+
+// The register + LDS-slot kernels, one block per CU: k_q1_stats_rl (1024 / NT rows per 16-wave
+// block) or k_q1_stats_wide (one row per 8-wave block).  GROUP: a row slot holds a segment.
+template <typename LT, bool DEC, bool GROUP>
+static int q1_slot_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Plan &p) {
+    const bool wide = p.family == Q1_WIDE || p.family == Q1_WIDE_GROUP;
+    const int64_t nrb = wide ? 1 : 1024 / p.nt, need = (a.rows + nrb - 1) / nrb;
+    unsigned grid = (unsigned)(need < c->cus ? need : c->cus);
+    int rpx = 0, rc;
+    if (GROUP && (rc = q1_group_setup(c, a, st, p.group, DEC, &grid, &rpx))) return rc;
+#define LAC_Q1_SLOT_ARGS LAC_Q1_ARGS, GROUP ? c->pxch : nullptr, GROUP ? p.group.split : 0, GROUP ? p.group.k : 1, rpx
+#define LAC_Q1_RL(REP, LASTN, NT)                       \
+    if (p.rep == REP && p.lastn == LASTN && p.nt == NT) \
+    k_q1_stats_rl<LT, DEC, REP, LASTN, NT, GROUP><<<grid, 1024, 0, st>>>(LAC_Q1_SLOT_ARGS)
     {
         ProfScope ps(c, KID_Q1_STATS, st);
-        k_q1_stats_rl<LT, DEC, REP, LASTN, NT, true><<<grid, 1024, 0, st>>>(
-            (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-            c->q1chunks, c->q1m, c->pxch, g.split, g.k, (int)rpx);
-        CHECK_LAUNCH();
-    }
-    // repair: the tiled two-pass shape over the same rows, gated on the abort word
-    // (its blocks exit at once when the groups completed: one small launch per job)
-    const uint64_t *gate = c->pxch + 2 * NRB * grid;
-    c->xch_abort = 2 * NRB * (int64_t)grid;
-    if (DEC) return q1_stats_launch<LT, 16, 16, DEC, true, false, 16>(c, a, st, gate);            // shape 10
-    if (sizeof(LT) == 4) return q1_stats_launch<LT, 16, 8, DEC, true, true, 16>(c, a, st, gate);  // shape 14
-    return q1_stats_launch<LT, 8, 8, DEC, true, false>(c, a, st, gate);                            // shape 8
-}
-
-template <typename LT, bool DEC>
-static int q1_stats_group_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Group &g) {
-    if (g.nrb == 4) {
-        if constexpr (!DEC)
-            if (g.rep16) return q1_group_kernel<LT, DEC, 16, 192, 256>(c, a, st, g);
-        return q1_group_kernel<LT, DEC, kRLRep, 256, 256>(c, a, st, g);
-    }
-    if (g.nrb == 2) {
-        if (g.rep16) return q1_group_kernel<LT, DEC, 16, 320, 512>(c, a, st, g);
-        return q1_group_kernel<LT, DEC, kRLRep, 512, 512>(c, a, st, g);
-    }
-    if (g.rep16) return q1_group_kernel<LT, DEC, 16, kRLLastTrim, 1024>(c, a, st, g);
-    return q1_group_kernel<LT, DEC, kRLRep, 1024, 1024>(c, a, st, g);
-}
-
-// Shape 23: rows of > 20480 vectors in kg = ceil(vectors / 20480) segments of one
-// 8-wave block each (k_q1_stats_wide's GROUP form); false when the row would need
-// more segments than an XCD's CUs.
-static bool q1_wide_group(lac_ctx *c, int64_t nvec, Q1Group *g) {
-    const int64_t ngrp = (nvec + 63) / 64, spx = c->cus / 8;
-    for (int k = (int)((nvec + kQ1WideMaxVec - 1) / kQ1WideMaxVec); k <= kQ1MaxSeg && k <= spx; k++) {
-        const int64_t sp = 64 * ((ngrp + k - 1) / k), last = nvec - (k - 1) * sp;
-        if (k >= 2 && last > 0 && sp <= kQ1WideMaxVec && last <= kQ1WideMaxVec) {
-            g->k = k;
-            g->split = (int)sp;
-            g->nrb = 1;
-            return true;
+        if (wide && (GROUP || !p.wide_slots)) {
+            k_q1_stats_wide<LT, kQ1WideR, DEC, GROUP><<<grid, 512, 0, st>>>(LAC_Q1_SLOT_ARGS);
+        } else if (wide) {                                       // rows past the registers: + LDS slots
+            if constexpr (!GROUP)
+                k_q1_stats_wide<LT, kQ1WideR, DEC, false, kQ1WideL><<<grid, 512, 0, st>>>(LAC_Q1_SLOT_ARGS);
+        } else LAC_Q1_RL(16, kRLLastTrim, 1024);                 // one row per block (shapes 15 / 19)
+        else LAC_Q1_RL(kRLRep, 1024, 1024);
+        else LAC_Q1_RL(16, 320, 512);                            // two (18 / 20) -- LDS: 2 x 61 KB of slots + 16 copies
+        else LAC_Q1_RL(kRLRep, 512, 512);
+        else LAC_Q1_RL(kRLRep, 256, 256);                        // four (17 / 21) -- LDS: 4 x 31 KB of slots + 8 copies,
+        else if constexpr (!DEC) {                               // or a trimmed last slot + 16 copies (encode) /
+            LAC_Q1_RL(16, 192, 256);                             // 8 beside the group totals (decode's shape 17;
+        } else if constexpr (!GROUP) {                           // its groups have no trimmed form)
+            LAC_Q1_RL(kRLRep, 192, 256);
         }
-    }
-    return false;
-}
-
-template <typename LT, bool DEC>
-static int q1_wide_group_kernel(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Group &g) {
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    if (!c->pxch) HIPCHK(hipMalloc(&c->pxch, sizeof(uint64_t) * (8 * (int64_t)c->cus + 1)));
-    // rpx rows per XCD per round on rpx * k blocks of the XCD (one per CU: every member resident)
-    const int64_t spx = (int64_t)(c->cus / 8), rcap = spx / g.k, rneed = (a.rows + 7) / 8;
-    const int64_t rpx = rneed < rcap ? rneed : rcap;
-    const unsigned grid = (unsigned)(8 * rpx * g.k);
-    HIPCHK(hipMemsetAsync(c->pxch, 0, sizeof(uint64_t) * (2 * (int64_t)grid + 1), st));
-    if (DEC) HIPCHK(hipMemsetAsync(c->q1chunks, 0, sizeof(uint64_t) * 64 * a.rows, st));
-    else HIPCHK(hipMemsetAsync(c->stats, 0, sizeof(RowStats) * a.rows, st));
-    {
-        ProfScope ps(c, KID_Q1_STATS, st);
-        k_q1_stats_wide<LT, kQ1WideR, DEC, true><<<grid, 512, 0, st>>>(
-            (const LT *)a.lg, a.ss, a.bs, a.sym, c->B, a.rows, c->V, a.t0, a.xsh, q1_groups_per_chunk(nvec), c->stats,
-            c->q1chunks, c->q1m, c->pxch, g.split, g.k, (int)rpx);
         CHECK_LAUNCH();
     }
-    // repair: the tiled two-pass shape, gated on the abort word (as q1_group_kernel)
-    const uint64_t *gate = c->pxch + 2 * (int64_t)grid;
-    c->xch_abort = 2 * (int64_t)grid;
-    if (DEC) return q1_stats_launch<LT, 16, 16, DEC, true, false, 16>(c, a, st, gate);            // shape 10
-    if (sizeof(LT) == 4) return q1_stats_launch<LT, 16, 8, DEC, true, true, 16>(c, a, st, gate);  // shape 14
-    return q1_stats_launch<LT, 8, 8, DEC, true, false>(c, a, st, gate);                            // shape 8
+#undef LAC_Q1_RL
+#undef LAC_Q1_SLOT_ARGS
+    if constexpr (GROUP) return q1_group_repair<LT, DEC>(c, a, st, p, grid);
+    return LAC_OK;
 }
 
-// The register + LDS-slot shapes (k_q1_stats_rl), by rows per block:
-//   15 = one row of <= 16384 vectors (16 table copies when <= 16064: trimmed last slot, else 8),
-//   17 = four rows of <= 4096 vectors (4 waves each), 18 = two rows of <= 8192 (8 waves each).
-// A trimmed last slot (whole waves only) makes room for 16 table copies where the LDS allows it.
 template <typename LT, bool DEC>
-static int q1_stats_rl_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, int shape) {
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    switch (shape) {
-    case 15:
-        if (nvec <= kRLTrimMaxVec) return q1_rl_kernel<LT, DEC, 16, kRLLastTrim, 1024>(c, a, st);
-        return q1_rl_kernel<LT, DEC, kRLRep, 1024, 1024>(c, a, st);
-    case 17:                                       // LDS: 4 x 31 KB of slots + 16 copies (encode) / 8 (decode)
-        if (nvec <= 15 * 256 + 192) return q1_rl_kernel<LT, DEC, DEC ? 8 : 16, 192, 256>(c, a, st);
-        return q1_rl_kernel<LT, DEC, kRLRep, 256, 256>(c, a, st);
-    default:                                       // 18 -- LDS: 2 x 61 KB of slots + 16 copies
-        if (nvec <= 15 * 512 + 320) return q1_rl_kernel<LT, DEC, 16, 320, 512>(c, a, st);
-        return q1_rl_kernel<LT, DEC, kRLRep, 512, 512>(c, a, st);
-    }
-}
-
-// Row-group shapes (waves per row RW, 16-B vectors per thread R, rolling
-// prefetch) of k_q1_stats.  AUTO takes the first listed shape that holds the row
-// in registers (measured on MI355X, c3 shape: encode bf16 (8,8,y) 0.75 ms vs
-// (8,8,n) 0.79 ms; decode (8,8,n) 70 M sym/s vs 46 M for the spilling (8,8,y)),
-// else tiles of (8, 8); LAC_OPT_Q1_SHAPE forces one for both directions (tuning;
-// identical results).  10 = tiles of a 16-wave (16,16,n) block per CU, 14 = tiles of
-// (16,8) with a rolling prefetch that walks the tiles (pass 1 up, pass 2 down, then
-// the next row's first tile).
-//
-// Round 4 retired the shapes AUTO never reaches (5, 7, 9, 11, 12, 13, 16): each vocabulary
-// range resolves to one of 1..4 / 6 (rows <= 4096 vectors), 17 / 18 (<= 8192), 15
-// (<= 16384), 22 (<= 26112), 19..21 / 23 (longer) or the tiled fallbacks 8 / 10 / 14,
-// and a forced retired number is refused (LAC_E_ARG) instead of running a form no
-// default configuration exercises.  Their measurements stay in DESIGN.md section 5b.
-static const int kQ1Shapes[][3] = {{1, 4, 0}, {2, 8, 0}, {4, 8, 0}, {8, 8, 0}, {8, 16, 0}, {8, 8, 1}, {8, 4, 1}};
-bool q1_shape_live(int sh) {
-    return sh >= 0 && sh <= 23 && sh != 5 && sh != 7 && sh != 9 && sh != 11 && sh != 12 && sh != 13 && sh != 16;
+static int q1_launch(lac_ctx *c, const Q1Args &a, hipStream_t st, const Q1Plan &p) {
+    if (p.family == Q1_TILED) return q1_tiled_launch<LT, DEC>(c, a, st, p);
+    if (p.family == Q1_RL || p.family == Q1_WIDE) return q1_slot_launch<LT, DEC, false>(c, a, st, p);
+    return q1_slot_launch<LT, DEC, true>(c, a, st, p);
 }
 
 template <typename LT, bool DEC>
 static int q1_stats(lac_ctx *c, const Q1Args &a, hipStream_t st) {
-    const int64_t nvec = c->V / LogitN<LT>::N;
-    int sh = c->q1_shape;
-    auto holds = [&](int i) { return nvec <= 64 * kQ1Shapes[i - 1][0] * kQ1Shapes[i - 1][1]; };
-    if (sh == 0) {
-        // both directions take the prefetching (8,8) form 6 at 2049..4096 vectors: its decode
-        // form spilled around the 8-way multi-sum (4 instead, no prefetch) until round 5
-        // streamed the butterfly (127 VGPRs, no spills; profiles/r05/q1dec_pf/)
-        static const int enc_order[] = {1, 2, 3, 6}, dec_order[] = {1, 2, 3, 6};
-        // several rows per 16-wave block in registers + LDS slots (shapes 17 / 18; same-box,
-        // profiles/r02/q1_rl_rows/): rows of 4097..8192 vectors in both directions (bf16
-        // V = 65536 encode 1.48 -> 1.31 ms, f32 c3 1.241 -> 1.200 ms = 87 % of peak, decode
-        // stats 2-3 % faster), f32 rows of 2049..4096 vectors in encode (V = 16384: 0.678 ->
-        // 0.621 ms).  bf16 c3 keeps shape 6 to encode (0.651 vs 0.660 ms) and 4 to decode.
-        if (nvec > 4096 && nvec <= 8192) sh = 18;
-        else if (!DEC && sizeof(LT) == 4 && nvec > 2048 && nvec <= 4096) sh = 17;
-        for (int i : DEC ? dec_order : enc_order) {
-            if (sh) break;
-            if (holds(i)) { sh = i; break; }
-        }
-        // rows of 8193..16384 vectors: registers + LDS slots (shape 15; same-box, bf16
-        // V = 128256 encode 3.23 -> 2.49 ms = 84 % of peak, f32 V = 65536 encode 2.73 ->
-        // 2.43 ms, decode 21.5 -> 24.0 M sym/s, profiles/r02/q1_rl/; bf16 decode, once its
-        // spills were removed (streamed butterfly, per-group LDS totals, fresh lane index),
-        // 220 -> 210 us per step of 4096 rows vs shape 9, profiles/r02/q1_rl_dec/)
-        if (sh == 0 && nvec <= 16384) sh = 15;
-        // rows of 16385..20480 vectors: one row per CU in the registers of an 8-wave
-        // block with a rolling prefetch (shape 22; same-box vs row groups,
-        // profiles/r03/wide/prefetch/: bf16 V = 151936 (Qwen2) 70.8 -> 85.6 % of peak,
-        // decode stats 270 -> 184-216 us per step; bf16 131080 63 -> 73 %; f32 65540
-        // 71.7 -> 80.5 %)
-        // Rows of 20481..26112 vectors add 11 vectors per thread in LDS slots (same box,
-        // profiles/r03/vocabs/: bf16 V = 202048 (Llama-4) 66.9 -> 81.1 %, bf16 200024
-        // (o200k) 65.8 -> 76.0 %, f32 100280 (cl100k) 72.4 -> 80.4 %, f32 102400
-        // (DeepSeek) 78.5 -> 86.7 %; f32 decode stats 8-11 % faster).  The bf16 decode form
-        // spilled 21 VGPRs there until round 4 (hoisted LDS-DMA offsets and per-batch bin
-        // addresses, now recomputed where used): spill-free, bf16 V = 202048 decode stats
-        // 313 -> 269 us per step (65.9 -> 76.9 % of peak), 200024 317 -> 275 us
-        // (profiles/r04/ab_dec/), so AUTO takes it in both directions
-        if (sh == 0 && nvec <= kQ1WideSlotMaxVec) sh = 22;
-        // longer rows: row groups (shapes 19 / 20 / 21: segments in row slots of 1 / 2 / 4
-        // rows per block), the form that keeps the most bytes in flight (q1_group).
-        // Round 2 had whole blocks per segment (kg = 2..4 blocks of 1 or 2 rows): bf16
-        // V = 256000 48 -> 78 % of peak (profiles/r02/q1_pair_bf16/), Qwen2 bf16 57 -> 65 %
-        // (profiles/r02/q1_groups2/); row slots at any kg: profiles/r03/q1_slots/
-        Q1Group grp;
-        if (sh == 0 && nvec > 16384 && q1_group(c, nvec, DEC, sizeof(LT) == 2, 0, &grp)) {
-            // where the best slot form has several rows per block, rows go to groups of
-            // 8-wave blocks instead (shape 23; same box, profiles/r03/wide/group/: bf16
-            // V = 262144 68.6 -> 80.1 % of peak (slots of the 4-row form before), f32
-            // 151936 79.6 -> 85.2 % (2-row form); one-row forms stay: bf16 256000 79.3 vs
-            // 77.8 %, f32 128256 83.7 vs 82.5 %, f32 262144 82.2 vs 82.1 %)
-            // ... and only where those blocks are well filled: segments of ~12500 vectors
-            // (f32 V = 100280 / 102400, bf16 200024 / 202048: 61-63 % of a block) ran at
-            // 58-70 % against 66-79 % in the slot forms (profiles/r03/vocabs/)
-            Q1Group wg;
-            if (grp.nrb > 1 && q1_wide_group(c, nvec, &wg) && nvec >= 0.75 * wg.k * kQ1WideMaxVec)
-                return q1_wide_group_kernel<LT, DEC>(c, a, st, wg);
-            return q1_stats_group_launch<LT, DEC>(c, a, st, grp);
-        }
-        // measured at V = 128256 f32: encode tiles of (16,8) with the tile-rolling
-        // prefetch 1.98 ms vs 2.18 for tiles of (8,8) (shape 13, its (8,8) form: 2.20)
-        // (rows of > 16384 vectors that no group form takes)
-        if (sh == 0) sh = DEC ? 10 : (sizeof(LT) == 4 ? 14 : 8);
-    }
-    if (sh == 10) return q1_stats_launch<LT, 16, 16, DEC, true, false, 16>(c, a, st);   // tiles of 16384
-    // registers + LDS slots (q1_stats_rl_launch): 15 one row of <= 16384 vectors per
-    // block, 17 four rows of <= 4096, 18 two rows of <= 8192
-    if (sh == 15 && nvec <= 16384) return q1_stats_rl_launch<LT, DEC>(c, a, st, sh);
-    if (sh == 17 && nvec <= 4096) return q1_stats_rl_launch<LT, DEC>(c, a, st, 17);
-    if (sh == 18 && nvec <= 8192) return q1_stats_rl_launch<LT, DEC>(c, a, st, 18);
-    Q1Group grp;
-    if (sh >= 19 && sh <= 21 && q1_group(c, nvec, DEC, sizeof(LT) == 2, sh == 19 ? 1 : sh == 20 ? 2 : 4, &grp))
-        return q1_stats_group_launch<LT, DEC>(c, a, st, grp);
-    if (sh == 22 && nvec <= kQ1WideSlotMaxVec) return q1_wide_launch<LT, DEC>(c, a, st);
-    if (sh == 23 && q1_wide_group(c, nvec, &grp)) return q1_wide_group_kernel<LT, DEC>(c, a, st, grp);
-    if (sh == 14) return q1_stats_launch<LT, 16, 8, DEC, true, true, 16>(c, a, st);    // tiles of (16,8,y)
-    if (sh == 8) return q1_stats_launch<LT, 8, 8, DEC, true, false>(c, a, st);      // tiles of 4096 vectors
-    // shapes 15, 17..23 with a row too long for them, and 1..4 / 6 likewise (kQ1Shapes
-    // describes 1..7 only; lac_set_option refuses the retired shapes)
-    if (sh > 7 || !q1_shape_live(sh) || !holds(sh))
-        return fail(LAC_E_ARG, "q1 shape %d does not hold a row of %lld vectors", sh, (long long)nvec);
-    switch (sh) {
-    case 1: return q1_stats_launch<LT, 1, 4, DEC, false, false>(c, a, st);
-    case 2: return q1_stats_launch<LT, 2, 8, DEC, false, false>(c, a, st);
-    case 3: return q1_stats_launch<LT, 4, 8, DEC, false, false>(c, a, st);
-    case 4: return q1_stats_launch<LT, 8, 8, DEC, false, false>(c, a, st);
-    default: return q1_stats_launch<LT, 8, 8, DEC, false, true>(c, a, st);   // 6
-    }
+    Q1Plan p;
+    if (q1_plan(c->cus, c->V, (int)sizeof(LT), DEC, c->q1_shape, &p))
+        return fail(LAC_E_ARG, "q1 shape %d does not hold a row of %lld vectors", c->q1_shape,
+                    (long long)(c->V / LogitN<LT>::N));
+    return q1_launch<LT, DEC>(c, a, st, p);
 }
 
 template <typename LT>

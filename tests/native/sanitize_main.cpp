@@ -3,7 +3,8 @@
 // built together with AddressSanitizer + UndefinedBehaviorSanitizer
 // (tests/native/Makefile, target `asan`) and cross-checked on seeded random
 // inputs: exact 128-bit division (incl. an inexact reciprocal), Python-rounded
-// ratios, whole encodes core vs oracle, oracle encode -> decode round trips.
+// ratios, whole encodes core vs oracle, oracle encode -> decode round trips; and
+// the kernel selection's sweeps (lac_select.h, through select_check.cpp).
 // Exit status 0 = every check passed and no sanitizer report.
 #include <math.h>
 #include <stdint.h>
@@ -32,6 +33,12 @@ int64_t lacref_decode_bitserial(const void *pmf, int elem_bytes, int64_t V, int6
 int cc_hc_encode_symbol(int prec, int64_t *l, int64_t *h, int64_t lo, int64_t hi, int8_t *digits, int32_t *n);
 int cc_hc_encode_flush(int prec, int64_t l, int64_t h, int8_t *digits, int32_t *n);
 int cc_hc_decode_emit(int prec, int64_t *regs, int64_t lo, int64_t hi, int renormalise);
+// kernel selection (lac_select.h through select_check.cpp)
+int sc_q1_plan(int cus, int64_t V, int type_bytes, int dec, int forced_shape, int64_t *o);
+int64_t sc_q1_slot_cap(int nrb, int rep16);
+int sc_q1_shape_live(int sh);
+void sc_decode_plan(const int64_t *kn, int64_t B, int64_t V, int pmf_bits, int prec, int aligned16,
+                    int64_t step_stride, int64_t stream_stride, int64_t steps, int64_t *o);
 }
 
 // ---- the reference's register arithmetic (arith_code.py:169-202, 274-291) in 128
@@ -103,7 +110,54 @@ static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); if (++fails > 20) exit(1); } } while (0)
 
+// The sweeps of tests/test_select_host.py over the kernel selection, so that its integer and
+// scoring arithmetic runs under the sanitizers: AUTO never fails and a group plan's segments
+// fit; a forced shape is that shape or refused; decode_plan over streams, vocabularies and knobs.
+static void select_sweep() {
+    enum { SHAPE, FAMILY, RW, R, MULTI, PF, NWB, REP, LASTN, NT, SLOTS, K, SPLIT, NRB, REP16, REPAIR, GPC, TSHAPE };
+    int64_t o[18];
+    for (int cus : {64, 256, 304})
+        for (int tb : {2, 4})
+            for (int dec = 0; dec < 2; dec++) {
+                const int n = 16 / tb;
+                for (int64_t V = n; V <= 300000; V += (V / n % 64 == 0 || V < 4 * n ? 1 : 331) * n) {
+                    const int64_t nvec = V / n;
+                    CHECK(sc_q1_plan(cus, V, tb, dec, 0, o) == 0, "q1 AUTO fails at V %lld", (long long)V);
+                    if (o[FAMILY] >= 3) {                       // the group forms
+                        const int64_t cap = o[FAMILY] == 4 ? 20480 : sc_q1_slot_cap((int)o[NRB], (int)o[REP16]);
+                        const int64_t last = nvec - (o[K] - 1) * o[SPLIT], slots = (int64_t)(cus / 8) * o[NRB];
+                        CHECK(o[SPLIT] % 64 == 0 && last > 0 && last <= cap && o[SPLIT] <= cap && o[K] >= 2 &&
+                                  o[K] <= 16 && o[K] <= slots && o[REPAIR] == o[TSHAPE],
+                              "q1 group at V %lld cus %d", (long long)V, cus);
+                    }
+                    for (int sh = -1; sh <= 24; sh++) {
+                        const int rc = sc_q1_plan(cus, V, tb, dec, sh, o);
+                        CHECK(rc == 0 || rc == -1, "q1 forced status");
+                        CHECK(rc != 0 || sh == 0 || o[SHAPE] == sh, "q1 forced shape %d gives %lld", sh, (long long)o[SHAPE]);
+                        CHECK(rc != 0 || sc_q1_shape_live(sh), "q1 retired shape %d accepted", sh);
+                        CHECK(rc == 0 || sh != 0, "q1 AUTO refused");
+                    }
+                }
+            }
+    for (int i = 0; i < 200000; i++) {
+        const int64_t kn[10] = {(int64_t)below(5), (int64_t)below(5000),     (int64_t)below(5000), (int64_t)below(600),
+                                (int64_t)below(600), (int64_t)below(20),     (int64_t)below(2),    (int64_t)below(2),
+                                (int64_t)below(2),   1 + (int64_t)below(1 << (int)below(24))};
+        const int bits = below(2) ? 32 : 64;
+        const int64_t B = 1 + (int64_t)below(1 << (int)below(14)), V = 1 + (int64_t)below(1 << (int)(1 + below(25)));
+        const int64_t steps = 1 + (int64_t)below(5000), ss = below(3) ? B * V : (int64_t)below(3), bs = V + (int64_t)below(3);
+        sc_decode_plan(kn, B, V, bits, 2 + (int)below(60), (int)below(2), ss, bs, steps, o);
+        const int vw = bits == 32 ? 4 : 2;
+        CHECK((o[0] == 0 || o[0] == -1) && o[1] >= 0 && o[1] <= 3 && (o[2] == 1 || o[2] == vw), "decode_plan fields");
+        if (o[1] == 3) CHECK(o[9] >= 1 && (!o[7] || (o[2] > 1 && o[8] >= 1 && o[8] <= 4 && B <= 44)), "decode_plan stats");
+        if (o[1] == 2) CHECK(o[2] > 1 && (o[4] == 4 || o[4] == 8 || o[4] == 16), "decode_plan block");
+        if (o[1] == 0) CHECK((o[5] == 8 || o[5] == (bits == 32 ? 2 : 4)) && (o[6] == 16 || o[6] == 4), "decode_plan step");
+    }
+    fprintf(stderr, "select ok\n");
+}
+
 int main() {
+    select_sweep();
     // exact floor division, also with the reciprocal 4 ULPs off
     for (int i = 0; i < 200000; i++) {
         const uint64_t d = 1 + (rnd() >> below(64));
