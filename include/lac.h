@@ -370,7 +370,11 @@ int lac_decode_steps(lac_ctx *ctx, const void *pmf_dev, int64_t step_stride, int
  * semantics are those of CDFPredictor + A_to_bin / A_from_bin
  * (arith_code.py:76-110, 156-334).  Logit rows: bf16 (uint16 bit patterns) or
  * f32, 16-byte aligned, vocab and strides (in elements) multiples of 8 (bf16)
- * or 4 (f32).  Requires the CEIL mapping and FLUSH termination. */
+ * or 4 (f32); a stride of 0 re-uses the row.  Any other layout -- a base off 16
+ * bytes, an odd row padding -- is refused with LAC_E_ARG by all four entry points
+ * below, before anything is launched or any stream's state changes (the integer
+ * pmf path takes such tables with its scalar kernels; this path has none).
+ * Requires the CEIL mapping and FLUSH termination. */
 #define LAC_LOGITS_BF16 1
 #define LAC_LOGITS_F32 2
 

@@ -330,3 +330,71 @@ def test_lean_u64_two_chunk_bounds_per_lane(V):
         c.decode_open(bits, nbits)
         assert np.array_equal(c.decode(dp).cpu().numpy(), sym), path
     c.close()
+
+
+# ---- LAC_OPT_DECODE_STOP with several streams stopping at different steps, and static rows
+
+_STOP_T, _STOP_EXTRA = 60, 40
+
+
+def _stop_case(B, prec, static, seed):
+    """u32 V = 1000 tables (minp 1; totals ~1.2e7, so at prec 24 -- widths in (2^23, 2^24] --
+    a row fudges on the steps whose width is below its total), 60 symbols per stream
+    encoded by the C oracle.  The bit buffer keeps every stream's real bits; only nbits is
+    cut, per stream: full, full, L/2, L-1, L/3, 8.  Expected per stream: the reference's
+    bit-serial run(bits, stop=0) restated (oracle.decode_bitserial) on those nbits, rows
+    past the end repeating the last.  -> (rows, bits, nbits, expected symbol lists)"""
+    from oracle import oracle as coracle
+    rng = np.random.default_rng(seed)
+    V, T = 1000, _STOP_T
+    rows = rng.integers(1, 24000, size=(1 if static else T, B, V)).astype(np.uint32)
+    rows[:, :, 7] = 1
+    sym = rng.integers(0, V, size=(T, B)).astype(np.int32)
+    out, onb, status, rc = coracle.encode_batch(np.ascontiguousarray(np.broadcast_to(rows, (T, B, V))), sym, prec)
+    assert rc == 0 and not status.any()
+    L = onb.astype(np.int64)
+    nbits = np.array([[L[b], L[b], L[b] // 2, L[b] - 1, L[b] // 3, 8][b % 6] for b in range(B)], dtype=np.int64)
+    want = [coracle.decode_bitserial(rows[:, b], out[b].tobytes(), int(nbits[b]), prec, max_out=T + _STOP_EXTRA)
+            for b in range(B)]
+    # the table outlasts every stream: no stop can hide behind the end of the decode
+    assert all(len(w) < T + _STOP_EXTRA for w in want), [len(w) for w in want]
+    for b in range(B):                                          # what the bits determine is a prefix of the message
+        n = min(len(want[b]), T)
+        assert want[b][:n] == sym[:n, b].tolist()
+    assert len({len(w) for w in want[:6]}) >= 4                 # the streams stop at different steps
+    stride = ((out.shape[1] + 7) // 8 + 1) * 8
+    buf = np.zeros((B, stride), dtype=np.uint8)
+    buf[:, :out.shape[1]] = out
+    return rows, buf, nbits, want
+
+
+@pytest.mark.parametrize("B,prec,static", [(6, 40, False), (6, 40, True), (6, 24, True), (70, 40, False)])
+def test_decode_stop_several_streams(B, prec, static):
+    """LAC_OPT_DECODE_STOP inside one launch: every stream stops by itself, at its own step,
+    before the first symbol its nbits do not determine, ignoring the real bits present past
+    nbits.  6 streams at prec 40 with per-step rows take the lean step with helpers; static
+    rows (stride-0 steps, [1, B, V] expanded) are one launch group, at prec 24 leaving the
+    lean step on the steps that fudge; 70 streams take k_decode_seq only.  All through the
+    k_decode_lean / k_decode_seq(max_steps = 1) / restart rounds and the per-stream hand-over."""
+    from lac_amd import _lib
+    from lac_amd.batch import BatchCoder
+    from lac_amd.coder import _DEC_STATE
+    import ctypes as C
+    rows, buf, nbits, want = _stop_case(B, prec, static, seed=1000 * B + prec + static)
+    V, T, N = 1000, _STOP_T, _STOP_T + _STOP_EXTRA
+    if static:
+        dp = _dev(rows).expand(N, B, V)
+    else:
+        dp = _dev(np.concatenate([rows, np.repeat(rows[-1:], _STOP_EXTRA, axis=0)]))
+    c = BatchCoder(V, B, prec=prec, capacity_bits=64, device=DEV)
+    c.set_decode_stop(True)
+    c.decode_open(torch.from_numpy(buf).to(DEV), torch.from_numpy(nbits).to(DEV))
+    out = c.decode(dp).cpu().numpy()
+    st = np.zeros(B, dtype=_DEC_STATE)
+    _lib.check(c.lib.lac_decode_get_state(c.ctx, st.ctypes.data_as(C.c_void_p), c._stream))
+    c.close()
+    for b in range(B):
+        n = len(want[b])
+        assert int(st["err"][b]) == _lib.LAC_E_UNDETERMINED, (b, st[b])
+        assert int(st["err_step"][b]) == n and int(st["nsym"][b]) == n and int(st["ndet"][b]) == n, (b, n, st[b])
+        assert out[:n, b].tolist() == want[b] and (out[n:, b] == -1).all(), (b, n)
