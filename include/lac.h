@@ -277,6 +277,39 @@ int lac_pack_jobs(int device, const uint64_t *planeA_dev, uint64_t plane_stride,
                   int64_t jobs, int64_t streams, uint64_t cap_words, uint8_t *dst_dev, uint64_t dst_bytes,
                   int hdr_bytes, const uint64_t *base_dev, uint64_t *ends_dev, uint64_t *lens_out, void *stream);
 
+/* The inverse of lac_pack_jobs, for the receiving side: one launch on `device`, asynchronous
+ * on `stream`, no context.  `jobs` packed jobs lie back to back from byte *base_dev (0 when
+ * NULL; device memory) of src_dev, each exactly as lac_pack_jobs writes it: a header of
+ * `streams` bit counts of hdr_bytes = 2 or 4 bytes each, then each stream's ceil(nbits / 8)
+ * bytes.  hdr_bytes = 0: the payload carries no header and job j's counts are
+ * counts_dev[j * streams + b] (required then, ignored otherwise): the body of a LAC1
+ * container (lac_amd.container), whose counts travel in its own header.  src_dev may have
+ * any alignment.  Stream b of job j is written at bits_dev + j * job_stride_bytes +
+ * b * stride_bytes in the form lac_decode_open takes -- the stream's bytes in memory order,
+ * then zeros: all stride_bytes of the slot are written -- and its bit count to
+ * nbits_dev[j * streams + b]; ends_dev[j] (may be NULL) receives the byte offset just past
+ * job j and status_dev[j] (may be NULL) the job's verdict.  Bytes between slots
+ * (stride_bytes * streams < job_stride_bytes) and everything outside the `jobs` regions are
+ * never written.  Source and destination must not overlap.
+ * The payload is untrusted: no load touches a byte outside [src_dev, src_dev + src_bytes)
+ * and no store falls outside a slot, whatever the counts claim (sums saturate).
+ *   A job whose header or payload would pass src_bytes: status LAC_E_ARG, ends_dev[j] = the
+ *   job's start, every stream's count UINT64_MAX and every slot zero; so for every later job
+ *   of the call (their start is unknown; ends_dev = that same start).  Earlier jobs are
+ *   unaffected.
+ *   A stream whose count exceeds 8 * stride_bytes: its slot is zero and its count the
+ *   claimed one (lac_decode_open then fails that stream with its sticky LAC_E_ARG), status
+ *   LAC_E_CAPACITY unless LAC_E_ARG applies; the job's other streams are unpacked.
+ * Refused with LAC_E_ARG before anything is launched: hdr_bytes not 0, 2 or 4; hdr_bytes = 0
+ * with counts_dev NULL; jobs < 0 (or > 65535) or streams <= 0; bits_dev, stride_bytes or
+ * job_stride_bytes not a multiple of 8; job_stride_bytes < streams * stride_bytes while
+ * jobs > 1; src_dev, bits_dev or nbits_dev NULL.  jobs = 0 is LAC_OK with no launch. */
+int lac_unpack_jobs(int device, const uint8_t *src_dev, uint64_t src_bytes, int hdr_bytes,
+                    const uint64_t *counts_dev, const uint64_t *base_dev,
+                    int64_t jobs, int64_t streams,
+                    uint8_t *bits_dev, uint64_t stride_bytes, uint64_t job_stride_bytes,
+                    uint64_t *nbits_dev, uint64_t *ends_dev, int32_t *status_dev, void *stream);
+
 /* Redirect where the context's encodes write their output: plane A (streams *
  * cap_words + 1 uint64, the packed bytes after the job) and the bit counts (streams
  * uint64), caller-owned device buffers that must outlive their use; NULL, NULL
@@ -345,6 +378,23 @@ int lac_encode_set_state(lac_ctx *ctx, const lac_enc_state *host_in, const uint6
  * and reads nothing. */
 int lac_decode_open(lac_ctx *ctx, const uint8_t *bits_dev, uint64_t stride_bytes,
                     const uint64_t *nbits_dev, void *stream);
+
+/* lac_decode_open straight from the wire: unpack one packed job (lac_unpack_jobs with
+ * jobs = 1 and the context's streams; src_dev, src_bytes, hdr_bytes, counts_dev, base_dev as
+ * there) into a buffer the context owns and open the decoder on it, both queued on `stream`
+ * with no host synchronisation.  The buffer -- streams slots of 8 * (ceil(capacity_bits / 64)
+ * + 1) bytes and streams counts -- is allocated on first use, freed by lac_close, and is not
+ * plane A: a pending encode output or an lac_set_output redirection is not disturbed.
+ * *end_dev (device memory, may be NULL) receives the offset past the job, so a receiver
+ * walks a payload of several jobs by passing it as the next base_dev.  The source is not
+ * borrowed: once the queued work has run the caller may overwrite it.  A job that does not
+ * fit src_bytes leaves every stream with the sticky LAC_E_ARG (lac_stream_status), a stream
+ * longer than the context's slots gets it alone.  Everything after the open -- every decode
+ * path, lac_set_stream_lengths, LAC_OPT_DECODE_STOP, the logits decode, lac_decode_get_state /
+ * lac_decode_set_state -- is what it is after lac_decode_open. */
+int lac_decode_open_packed(lac_ctx *ctx, const uint8_t *src_dev, uint64_t src_bytes, int hdr_bytes,
+                           const uint64_t *counts_dev, const uint64_t *base_dev, uint64_t *end_dev,
+                           void *stream);
 
 /* Decode one symbol per stream from row b at pmf_dev + b*stream_stride. */
 int lac_decode_step(lac_ctx *ctx, const void *pmf_dev, int64_t stream_stride,

@@ -59,6 +59,8 @@ PROTOTYPES = [
     ("lac_pack_bits", _i, [_vp, _vp, C.c_int, _vp, _vp]),
     ("lac_pack_bits_at", _i, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp, _vp]),
     ("lac_pack_jobs", _i, [C.c_int, _vp, _u64, _vp, _i64, _i64, _u64, _vp, _u64, C.c_int, _vp, _vp, _vp, _vp]),
+    ("lac_unpack_jobs", _i, [C.c_int, _vp, _u64, C.c_int, _vp, _vp, _i64, _i64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("lac_decode_open_packed", _i, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp, _vp]),
     ("lac_set_output", _i, [_vp, _vp, _vp]),
     ("lac_host_alloc", _i, [_u64, C.POINTER(_vp), C.POINTER(_vp)]),
     ("lac_host_free", _i, [_vp]),

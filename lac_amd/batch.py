@@ -428,6 +428,42 @@ class BatchCoder:
         check(self.lib.lac_decode_open(self.ctx, C.c_void_p(bits.data_ptr()), bits.stride(0),
                                        C.c_void_p(nbits.data_ptr()), self._stream))
 
+    def decode_open_packed(self, payload, hdr_bytes, counts=None, base=None, end=None):
+        """decode_open straight from the wire (include/lac.h lac_decode_open_packed): one packed
+        job -- what :meth:`pack_bits` writes, ``hdr_bytes`` = 2 or 4; or with ``hdr_bytes`` = 0
+        the streams' bytes back to back and their bit counts in ``counts`` (an 8-byte integer
+        device tensor [streams]) -- is unpacked from the uint8 device tensor ``payload`` (any
+        alignment; its size bounds every read) into slots the coder owns, and the decoder opens
+        on them.  ``base`` / ``end``: one-element 8-byte integer device tensors or None; the job
+        starts at byte ``base[0]`` (0 when None) and ``end`` receives the offset just past it,
+        the next job's ``base``.  Asynchronous, no host sync, and nothing is borrowed: once the
+        queued work has run ``payload`` may be overwritten.  A job that does not fit the
+        payload fails every stream with a sticky LAC_E_ARG, a stream longer than the coder's
+        capacity fails alone (:meth:`status`)."""
+        torch = _torch()
+        if hdr_bytes not in (0, 2, 4):
+            raise ValueError(f"hdr_bytes={hdr_bytes}: 2 or 4, or 0 with counts")
+        if payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous() \
+                or payload.device != self.device:
+            raise ValueError(f"payload must be a contiguous 1-D uint8 device tensor on {self.device}")
+        if payload.numel() == 0:
+            raise ValueError("payload is empty")
+        if hdr_bytes == 0:
+            if counts is None or counts.element_size() != 8 or counts.is_floating_point() \
+                    or counts.device != self.device:
+                raise ValueError("hdr_bytes=0 needs counts: an 8-byte integer tensor on the coder's device")
+            if tuple(counts.shape) != (self.streams,) or not counts.is_contiguous():
+                raise ValueError(f"counts must be a contiguous [{self.streams}] tensor")
+        for t in (base, end):
+            if t is not None and (t.numel() < 1 or t.element_size() != 8 or t.device != self.device):
+                raise ValueError("base / end must be 8-byte integer tensors on the coder's device")
+        check(self.lib.lac_decode_open_packed(self.ctx, C.c_void_p(payload.data_ptr()), payload.numel(),
+                                              int(hdr_bytes),
+                                              C.c_void_p(counts.data_ptr()) if hdr_bytes == 0 else None,
+                                              None if base is None else C.c_void_p(base.data_ptr()),
+                                              None if end is None else C.c_void_p(end.data_ptr()), self._stream))
+        self._dec_keep = None                                 # the decoder reads the coder's own slots
+
     def determined(self):
         """Per stream: leading decoded symbols fixed by the available bits (the
         count the reference's A_from_bin.run(bits, stop=0) emits)."""

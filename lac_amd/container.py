@@ -108,29 +108,48 @@ def decompress_batch(blob: bytes, pmf, device=None):
     """Decode a container produced by :func:`compress_batch` given the same tables
     (the same logits for a q1 container).  -> (out [max(n_symbols), streams] int32, n_symbols);
     where the streams' counts differ, out is -1 past each stream's count."""
-    import numpy as np
     import torch
 
     from .batch import BatchCoder
-    h = unpack(blob)
-    B = len(h["streams"])
-    steps = max(h["n_symbols"]) if B else 0
-    stride = max(8, ((max((len(s) for s in h["streams"]), default=0) + 7) // 8 + 1) * 8)
-    buf = np.zeros((B, stride), dtype=np.uint8)
-    for b, s in enumerate(h["streams"]):
-        buf[b, :len(s)] = np.frombuffer(s, dtype=np.uint8)
+    h, n_symbols, n_bits, body = _index(blob)
+    B = len(n_bits)
+    steps = int(n_symbols.max()) if B else 0
     coder = BatchCoder(h["vocab"], B, prec=h["prec"], pmf_bits=h["pmf_bits"],
-                       capacity_bits=max(h["n_bits"], default=64) + 64, device=device or pmf.device)
+                       capacity_bits=(int(n_bits.max()) if B else 64) + 64, device=device or pmf.device)
     coder.set_mapping(h["mapping"])
-    bits = torch.from_numpy(buf).to(coder.device)
-    nb = torch.tensor(h["n_bits"], dtype=torch.int64, device=coder.device)
+    # the body as it is -- the streams' bytes back to back, the wire format without a header --
+    # and the counts go up; the coder unpacks them into its slots on the device
+    # (BatchCoder.decode_open_packed): no per-stream work here
+    payload = torch.frombuffer(bytearray(body) or bytearray(8), dtype=torch.uint8).to(coder.device)
+    nb = torch.from_numpy(n_bits.astype("<i8")).to(coder.device)
     # a ragged container: each stream decodes its own count and no further (out is -1 past it)
-    if any(n != steps for n in h["n_symbols"]):
-        coder.set_stream_lengths(h["n_symbols"])
-    coder.decode_open(bits, nb)
+    if B and bool((n_symbols != steps).any()):
+        coder.set_stream_lengths(n_symbols)
+    coder.decode_open_packed(payload, 0, counts=nb)
     if h["q1_logits"] != _is_logits(pmf):
         raise ValueError("container and tables disagree: q1 logits vs integer pmf")
     out = coder.decode_logits(pmf[:steps]) if h["q1_logits"] else coder.decode(pmf[:steps])
     coder.raise_on_error()
     coder.close()
-    return out, h["n_symbols"]
+    return out, n_symbols.tolist()
+
+
+def _index(blob):
+    """The container's header and count table without slicing the streams: -> (header fields
+    as :func:`unpack` names them, n_symbols uint64 [streams], n_bits uint64 [streams], body);
+    raises what :func:`unpack` raises for a blob that is not a whole container."""
+    import numpy as np
+    magic, ver, prec, flags, vocab, ns = _HDR.unpack_from(blob, 0)
+    off = _HDR.size + ns * _ENT.size
+    if magic != MAGIC or ver != VERSION or len(blob) < off:
+        unpack(blob)                                           # raises for each of these
+    ent = np.frombuffer(blob, dtype="<u8", count=2 * ns, offset=_HDR.size).reshape(ns, 2)
+    n_bits = ent[:, 1]
+    nbytes = (n_bits >> np.uint64(3)) + ((n_bits & np.uint64(7)) != 0).astype(np.uint64)
+    # (a count beyond the blob cannot match, and without one the uint64 sum cannot wrap)
+    if ns and (int(nbytes.max()) > len(blob) or off + int(nbytes.sum()) != len(blob)) or not ns and off != len(blob):
+        raise ValueError("trailing bytes in container")
+    h = {"prec": prec, "vocab": vocab, "mapping": "floor" if flags & 1 else "ceil",
+         "termination": "acsampler" if flags & 2 else "flush", "pmf_bits": 64 if flags & 4 else 32,
+         "q1_logits": bool(flags & 8)}
+    return h, ent[:, 0], n_bits, memoryview(blob)[off:]

@@ -95,6 +95,8 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->q1m);
     (void)hipFree(c->pxch);
     (void)hipFree(c->slen);
+    (void)hipFree(c->ubits);
+    (void)hipFree(c->unbits);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;

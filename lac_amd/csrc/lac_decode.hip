@@ -1615,6 +1615,24 @@ int lac_decode_open(lac_ctx *c, const uint8_t *bits_dev, uint64_t stride_bytes, 
     return LAC_OK;
 }
 
+int lac_decode_open_packed(lac_ctx *c, const uint8_t *src_dev, uint64_t src_bytes, int hdr_bytes,
+                           const uint64_t *counts_dev, const uint64_t *base_dev, uint64_t *end_dev, void *stream) {
+    if (!c) return fail(LAC_E_ARG, "ctx is NULL");
+    if (!src_dev) return fail(LAC_E_ARG, "src_dev is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    // the context's own slots, apart from plane A: a pending encode output or an
+    // lac_set_output redirection stays as it is
+    const uint64_t stride = c->cap_words * 8;
+    if (!c->ubits) HIPCHK(hipMalloc(&c->ubits, stride * (uint64_t)c->B));
+    if (!c->unbits) HIPCHK(hipMalloc(&c->unbits, sizeof(uint64_t) * c->B));
+    const int rc = lac_unpack_jobs(c->device, src_dev, src_bytes, hdr_bytes, counts_dev, base_dev, 1, c->B, c->ubits,
+                                   stride, stride * (uint64_t)c->B, c->unbits, end_dev, nullptr, stream);
+    if (rc) return rc;
+    // a job that does not fit left every count at ~0, an over-long stream its claimed count:
+    // k_dec_init fails those streams with the sticky LAC_E_ARG
+    return lac_decode_open(c, c->ubits, stride, c->unbits, stream);
+}
+
 static_assert(sizeof(lac_dec_state) == sizeof(DecState) && offsetof(lac_dec_state, ndet) == offsetof(DecState, ndet) &&
                   offsetof(lac_dec_state, det) == offsetof(DecState, det) &&
                   offsetof(lac_dec_state, pos) == offsetof(DecState, pos),

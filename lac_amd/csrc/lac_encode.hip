@@ -13,7 +13,10 @@
 //   k_finish      flush (:193-202), carry resolution of bits() (:227-246), MSB-first
 //                 byte packing of group_bits (:336-347), one lane per stream.
 //   k_pack        the multi-GPU gather's payload (lac_pack_jobs, lac_amd/dist.py).
+//   k_unpack      its inverse: packed jobs -> the aligned slots the decoders read
+//                 (lac_unpack_jobs, lac_decode_open_packed; rules in lac_wire.h).
 #include "lac_host.h"
+#include "lac_wire.h"
 
 #include <type_traits>
 
@@ -515,6 +518,136 @@ __global__ __launch_bounds__(1024) void k_pack(const uint64_t *__restrict__ plan
     }
 }
 
+// lac_unpack_jobs / lac_decode_open_packed: the inverse of k_pack, one launch for `jobs`
+// packed jobs lying back to back from byte *base_in of src (lac_wire.h has the format and
+// every rule; wire_unpack_host there is this kernel in plain loops).  Workgroup (x, j, z)
+// holds streams [256 x, 256 x + 256) of job j.  Like k_pack it derives its own offsets, so
+// none waits on another: it walks the headers of jobs 0..j -- each job's header is tested
+// against src_bytes before a count is read, its counts are summed by the 256 threads
+// (saturating; L2-hot) and the payload is tested before the next job's start is believed --
+// then sums its job's streams before its tile and scans its own 256.  A job that does not
+// fit ends the walk: it and every later job get LAC_E_ARG, counts of ~0 and zero slots.
+// The copy is not one stream per thread (one long stream would be one lane's work): the
+// tile's slots are one run of 8-byte words, and the threads stride over it -- over
+// (stream, word) pairs while a slot is shorter than the workgroup, else stream by stream
+// over the words of each, split over gridDim.z workgroups for long slots.  Every word is
+// stored aligned and coalesced; its source is wire::slot_word: an 8-byte load at any
+// alignment that covers only the stream's own bytes, byte loads for the last partial word,
+// zero past the stream.  So no load leaves [src, src + src_bytes) and no store a slot.
+constexpr int kUnpackThreads = 256;
+
+__device__ inline uint64_t unpack_sat_sum(uint64_t v, uint64_t *wsum) {
+    const uint64_t s = wave_reduce(v, [](uint64_t a, uint64_t b) { return wire::sat_add(a, b); });
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    uint64_t total = 0;
+    for (int i = 0; i < kUnpackThreads / 64; i++) total = wire::sat_add(total, wsum[i]);
+    __syncthreads();
+    return total;
+}
+
+// exclusive prefix over the workgroup in plain sums (the caller knows they cannot wrap)
+__device__ inline uint64_t unpack_excl_scan(uint64_t v, uint64_t *wsum) {
+    const int w = threadIdx.x >> 6;
+    const uint64_t inc = wave_incl_scan_u64(v);
+    if ((threadIdx.x & 63) == 63) wsum[w] = inc;
+    __syncthreads();
+    uint64_t before = 0;
+    for (int i = 0; i < kUnpackThreads / 64; i++) before += i < w ? wsum[i] : 0;
+    __syncthreads();
+    return before + inc - v;
+}
+
+// One job's counts summed by the workgroup's threads, each its share: the byte counts of all
+// streams, of those before the tile, and whether a stream overflows its slot (the last two
+// for the workgroup's own job).  The header size is a template argument and the loop is
+// unrolled so that 8 counts' loads are in flight: the walk is latency-bound.
+template <int HDR>
+__device__ inline void unpack_sum_counts(const uint8_t *__restrict__ src, uint64_t start,
+                                         const uint64_t *__restrict__ ck, int64_t B, int64_t first, bool own,
+                                         uint64_t stride, uint64_t &all, uint64_t &pw, int &ov) {
+#pragma unroll 8
+    for (int64_t b = threadIdx.x; b < B; b += kUnpackThreads) {
+        const uint64_t nb = wire::read_count(src, start, HDR, ck, b);
+        const uint64_t m = wire::stream_bytes(nb);
+        all = wire::sat_add(all, m);
+        pw = wire::sat_add(pw, own && b < first ? m : 0);
+        ov |= own && !wire::stream_fits(nb, stride);
+    }
+}
+
+__global__ __launch_bounds__(kUnpackThreads) void k_unpack(const uint8_t *__restrict__ src, uint64_t src_bytes, int hdr,
+                                                           const uint64_t *__restrict__ counts,
+                                                           const uint64_t *__restrict__ base_in, int64_t B,
+                                                           uint8_t *__restrict__ bits, uint64_t stride,
+                                                           uint64_t job_stride, uint64_t *__restrict__ nbits_out,
+                                                           uint64_t *__restrict__ ends, int32_t *__restrict__ status) {
+    constexpr int T = kUnpackThreads;
+    __shared__ uint64_t wsum[T / 64];
+    __shared__ uint64_t s_off[T], s_n[T];
+    const int t = threadIdx.x;
+    const int64_t job = blockIdx.y, first = (int64_t)blockIdx.x * T;
+    wire::Walk w{base_in ? *base_in : 0, true};
+    uint64_t before = 0, end = 0;
+    int over = 0;
+    // every value that steers this loop is the same in all threads (sums through LDS)
+    for (int64_t k = 0; k <= job; k++) {
+        if (!wire::walk_header(w, hdr, B, src_bytes)) break;
+        const uint64_t *ck = counts ? counts + k * B : nullptr;
+        uint64_t all = 0, pw = 0;
+        int ov = 0;
+        if (hdr == 2) unpack_sum_counts<2>(src, w.start, ck, B, first, k == job, stride, all, pw, ov);
+        else if (hdr == 4) unpack_sum_counts<4>(src, w.start, ck, B, first, k == job, stride, all, pw, ov);
+        else unpack_sum_counts<0>(src, w.start, ck, B, first, k == job, stride, all, pw, ov);
+        const uint64_t payload = unpack_sat_sum(all, wsum);
+        if (!wire::walk_payload(w, hdr, B, payload, src_bytes)) break;
+        if (k < job) {
+            w.start = wire::job_end(w, hdr, B, payload);
+        } else {
+            before = unpack_sat_sum(pw, wsum);
+            over = __syncthreads_or(ov);
+            end = wire::job_end(w, hdr, B, payload);
+        }
+    }
+    const int64_t b = first + t;
+    uint64_t nb = wire::kNone, m = 0;
+    bool sf = false;
+    if (w.fits && b < B) {
+        nb = wire::read_count(src, w.start, hdr, counts ? counts + job * B : nullptr, b);
+        m = wire::stream_bytes(nb);
+        sf = wire::stream_fits(nb, stride);
+    }
+    // the job fits, so every partial sum of its byte counts is <= src_bytes: plain sums
+    const uint64_t excl = unpack_excl_scan(m, wsum);
+    s_off[t] = w.start + wire::header_bytes(hdr, B) + before + excl;
+    s_n[t] = sf ? m : 0;
+    if (blockIdx.z == 0) {
+        if (b < B) nbits_out[job * B + b] = nb;
+        if (blockIdx.x == 0 && t == 0) {
+            if (ends) ends[job] = w.fits ? end : w.start;
+            if (status) status[job] = wire::job_status(w.fits, over != 0);
+        }
+    }
+    __syncthreads();
+    const uint64_t W = stride >> 3;
+    const int64_t ns = B - first < T ? B - first : T;
+    uint64_t *dst = reinterpret_cast<uint64_t *>(bits + (uint64_t)job * job_stride + (uint64_t)first * stride);
+    if (W >= (uint64_t)T) {
+        const uint64_t chunk = (W + gridDim.z - 1) / gridDim.z;
+        const uint64_t lo = blockIdx.z * chunk, hi = lo + chunk < W ? lo + chunk : W;
+        for (int64_t s = 0; s < ns; s++) {
+            const uint64_t off = s_off[s], n = s_n[s];
+            for (uint64_t wi = lo + t; wi < hi; wi += T) dst[(uint64_t)s * W + wi] = wire::slot_word(src, off, n, wi);
+        }
+    } else {
+        const uint32_t Wn = (uint32_t)W, total = (uint32_t)ns * Wn;
+        for (uint32_t q = t; q < total; q += T) {
+            const uint32_t s = q / Wn, wi = q - s * Wn;
+            dst[q] = wire::slot_word(src, s_off[s], s_n[s], wi);
+        }
+    }
+}
+
 __global__ void k_enc_rebase(EncState *states, int64_t B) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -712,6 +845,27 @@ int lac_pack_jobs(int device, const uint64_t *planeA_dev, uint64_t plane_stride,
     k_pack<<<dim3(bx > 0 ? bx : 1, (unsigned)jobs), 1024, 0, S(stream)>>>(
         planeA_dev, plane_stride, cap_words, nbits_dev, streams, hdr_bytes, dst, dst_bytes, base_dev, ends_dev,
         lens_out);
+    CHECK_LAUNCH();
+    return LAC_OK;
+}
+
+int lac_unpack_jobs(int device, const uint8_t *src_dev, uint64_t src_bytes, int hdr_bytes, const uint64_t *counts_dev,
+                    const uint64_t *base_dev, int64_t jobs, int64_t streams, uint8_t *bits_dev, uint64_t stride_bytes,
+                    uint64_t job_stride_bytes, uint64_t *nbits_dev, uint64_t *ends_dev, int32_t *status_dev,
+                    void *stream) {
+    if (const char *why = wire::check_args(src_dev, hdr_bytes, counts_dev, jobs, streams, bits_dev, stride_bytes,
+                                           job_stride_bytes, nbits_dev))
+        return fail(LAC_E_ARG, "%s", why);
+    const int64_t tiles = (streams + kUnpackThreads - 1) / kUnpackThreads;
+    if (tiles > 0x7fffffff) return fail(LAC_E_ARG, "too many streams for one launch");
+    if (jobs == 0) return LAC_OK;
+    HIPCHK(hipSetDevice(device));
+    // long slots: up to 64 workgroups share each tile's words, 8 words or more per thread
+    const uint64_t W = stride_bytes / 8, per = 8 * kUnpackThreads;
+    const unsigned gz = W >= (uint64_t)kUnpackThreads ? (unsigned)((W + per - 1) / per < 64 ? (W + per - 1) / per : 64) : 1;
+    k_unpack<<<dim3((unsigned)tiles, (unsigned)jobs, gz), kUnpackThreads, 0, S(stream)>>>(
+        src_dev, src_bytes, hdr_bytes, hdr_bytes == 0 ? counts_dev : nullptr, base_dev, streams, bits_dev, stride_bytes,
+        job_stride_bytes, nbits_dev, ends_dev, status_dev);
     CHECK_LAUNCH();
     return LAC_OK;
 }

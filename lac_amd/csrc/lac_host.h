@@ -24,6 +24,8 @@ struct lac_ctx {
     const uint8_t *dbits = nullptr;
     uint64_t dstride = 0;
     const uint64_t *dnbits = nullptr;
+    uint8_t *ubits = nullptr;           // lac_decode_open_packed: [B][cap_words * 8] unpacked slots and
+    uint64_t *unbits = nullptr;         //                         [B] bit counts, allocated on first use
     int mode = 0;                       // 0 encode, 1 decode
     int finished = 0;                   // nbits / planeA hold finished streams (a job, lac_encode_finish)
     int open = 0;                       // streams hold coded symbols since the last reset and are not

@@ -161,6 +161,50 @@ def unpack_bitstreams(payload, streams, width, hdr_bytes):
     return out, nb
 
 
+def unpack_jobs(payload, jobs, streams, stride, hdr_bytes, counts=None, base=None):
+    """``jobs`` packed jobs lying back to back in the uint8 device tensor ``payload`` unpacked
+    by one kernel launch (include/lac.h lac_unpack_jobs; asynchronous on the current stream,
+    no host sync): the device form of :func:`unpack_bitstreams`, to whose result each job's
+    bits and counts are identical.  ``stride``: bytes per stream slot, a multiple of 8;
+    ``hdr_bytes`` 2 or 4, or 0 with ``counts`` (8-byte integer device tensor of jobs * streams
+    bit counts) for payloads without headers; ``base``: None or a one-element 8-byte integer
+    device tensor, the first job's byte offset.  ``payload.numel()`` bounds every read.
+    Returns (bits [jobs, streams, stride] uint8, nbits [jobs, streams] int64, ends [jobs]
+    int64: the offset past each job, status [jobs] int32: 0, or LAC_E_ARG for a job that does
+    not fit the payload -- its counts read -1, its slots zero, and so for every later job --
+    or LAC_E_CAPACITY where a stream's count exceeds 8 * stride: that slot is zero)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    dev = payload.device
+    if dev.type != "cuda" or payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous():
+        raise ValueError("payload must be a contiguous 1-D uint8 device tensor")
+    if payload.numel() == 0:
+        raise ValueError("payload is empty")
+    for t, n in ((counts, jobs * streams), (base, 1)):
+        if t is not None and (t.element_size() != 8 or t.is_floating_point() or t.device != dev
+                              or t.numel() < n or not t.is_contiguous()):
+            raise ValueError("counts / base must be contiguous 8-byte integer tensors on the payload's device")
+    if hdr_bytes == 0 and counts is None:
+        raise ValueError("hdr_bytes=0 needs counts")
+    bits = torch.empty((jobs, streams, stride), dtype=torch.uint8, device=dev)
+    nbits = torch.empty((jobs, streams), dtype=torch.int64, device=dev)
+    ends = torch.empty((jobs,), dtype=torch.int64, device=dev)
+    status = torch.empty((jobs,), dtype=torch.int32, device=dev)
+    if jobs == 0:
+        return bits, nbits, ends, status
+    _lib.check(_lib.load().lac_unpack_jobs(
+        dev.index or 0, C.c_void_p(payload.data_ptr()), payload.numel(), int(hdr_bytes),
+        C.c_void_p(counts.data_ptr()) if hdr_bytes == 0 else None,
+        None if base is None else C.c_void_p(base.data_ptr()), int(jobs), int(streams),
+        C.c_void_p(bits.data_ptr()), int(stride), int(streams) * int(stride), C.c_void_p(nbits.data_ptr()),
+        C.c_void_p(ends.data_ptr()), C.c_void_p(status.data_ptr()),
+        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return bits, nbits, ends, status
+
+
 def bitstreams_equal(got_bits, got_nbits, bits, nbits):
     """Whether an unpacked (zero padded) job ``got_*`` holds the streams ``bits`` /
     ``nbits`` (rows of a coder's output, any stride): equal bit counts, equal bytes over
@@ -549,7 +593,10 @@ class BitstreamGatherer:
         """Root: one job of the finished batches still held (``finished_jobs``; default
         the newest), rank by rank, as (bits [streams, width], nbits [streams]) with width
         the widest rank's slot.  A batch's bytes stay until its box is exchanged again,
-        so read them after the ``submit`` / ``drain`` that finished it."""
+        so read them after the ``submit`` / ``drain`` that finished it.  Device buffers with
+        slot widths in whole 8-byte words are unpacked by one launch per rank
+        (:func:`unpack_jobs`), anything else by the torch :func:`unpack_bitstreams`: the
+        same tensors either way."""
         import torch
         job = self.last_job if job is None else job
         last = next((b for b in self.recent if job in b["jobs"]), None)
@@ -560,7 +607,12 @@ class BitstreamGatherer:
         for r, row in enumerate(last["meta"]):
             off = sum(row[self.META:self.META + q])
             L = row[self.META + q]
-            parts.append(unpack_bitstreams(last["bufs"][r][off:off + L], row[1], row[2], row[3]))
+            part = last["bufs"][r][off:off + L]
+            if part.is_cuda and row[2] % 8 == 0 and row[1] > 0 and L > 0:   # one launch (lac_unpack_jobs)
+                b, n, _, _ = unpack_jobs(part, 1, row[1], row[2], row[3])
+                parts.append((b[0], n[0]))
+            else:                                                # host buffers (gloo), odd slot widths
+                parts.append(unpack_bitstreams(part, row[1], row[2], row[3]))
         W = max(p[0].shape[1] for p in parts)
         bits = [torch.nn.functional.pad(p[0], (0, W - p[0].shape[1])) for p in parts]
         return torch.cat(bits), torch.cat([p[1] for p in parts])
