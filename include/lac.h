@@ -108,12 +108,19 @@ enum {                       /* lac_set_option */
                                       rows <= 131072 u32 / 65536 u64 entries); 0 = <= 64 chunk totals */
     LAC_OPT_BLOCK_WAVES = 8,       /* BLOCK decode path: waves per stream (4, 8, 16; 0 = by stream
                                       count, the default) */
-    LAC_OPT_DECODE_STOP = 9        /* 1: a decoding stream stops before the first symbol its bits do
+    LAC_OPT_DECODE_STOP = 9,       /* 1: a decoding stream stops before the first symbol its bits do
                                       not determine (decide_symbol's ls != hs, arith_code.py:268-273)
                                       with LAC_E_UNDETERMINED, registers unchanged, instead of decoding
                                       on over zero padding; decodes then take the STATS path.  0 =
                                       off (default).  For decoders that stop where the reference's
                                       run(bits, stop=0) stops (lac_amd.coder.A_from_bin) */
+    LAC_OPT_Q1_STEP = 10           /* lac_decode_logits_step / lac_encode_logits_step: 0 = auto (default):
+                                      the fused one-launch step where it holds the job -- rows of
+                                      <= 16384 vectors (bf16 vocab <= 131072, f32 <= 65536) and few
+                                      enough streams --, else the two launches of the `steps = 1`
+                                      calls; 1 = fused (a shape it cannot take: LAC_E_ARG from the step
+                                      call, nothing launched, no state changed); 2 = the two-launch
+                                      path.  Identical results, only speed differs */
 };
 enum {
     LAC_MAP_CEIL = 0,              /* CDFPredictor.symbol_to_range + fudged_dist (arith_code.py:83-110) */
@@ -449,6 +456,23 @@ int lac_encode_logits(lac_ctx *ctx, const void *logits_dev, int logit_type, int6
 int lac_decode_logits_steps(lac_ctx *ctx, const void *logits_dev, int logit_type, int64_t step_stride,
                             int64_t stream_stride, int64_t steps, int32_t *sym_out_dev, void *stream);
 
+/* One position for a model in the loop: logits [streams][vocab] in (row b at logits_dev +
+ * b*stream_stride), one symbol per stream decoded or encoded.  Every observable equals the
+ * `steps = 1` call of lac_decode_logits_steps / lac_encode_logits (step_stride 0): symbols
+ * and -1 fills, lac_dec_state / lac_enc_state, planes, traces (trace_dev[2 b], may be NULL),
+ * sticky status and err_step, per-stream counts, and the same refusals before anything is
+ * launched; LAC_OPT_DECODE_STOP is ignored as the logits decode ignores it.  The calls mix
+ * freely with every other encode / decode call of a session.  Where the job fits
+ * (LAC_OPT_Q1_STEP) a position is one launch instead of two: one workgroup per stream holds
+ * the row in registers, computes its maximum, quantises it, scans it and runs the coder's
+ * step, with no row statistics written to memory in between.  Under lac_profile_read the
+ * fused decode step counts in slot 7 (q1_decode), the fused encode step in slot 1 (encode),
+ * and slot 6 (q1_stats) gets nothing. */
+int lac_decode_logits_step(lac_ctx *ctx, const void *logits_dev, int logit_type, int64_t stream_stride,
+                           int32_t *sym_out_dev /* [streams] */, void *stream);
+int lac_encode_logits_step(lac_ctx *ctx, const void *logits_dev, int logit_type, int64_t stream_stride,
+                           const int32_t *sym_dev /* [streams] */, uint64_t *trace_dev, void *stream);
+
 /* Rows longer than a CU holds (LAC_OPT_Q1_SHAPE 19 / 20 / 21 / 23, AUTO for e.g. f32 V =
  * 128256) are split over 2..16 row slots of workgroups that exchange each row's
  * maximum, which needs every member resident.  When a member is not (another
@@ -555,7 +579,9 @@ int lac_hc_decode_emit(int prec, int64_t *regs, int64_t lo, int64_t hi, int reno
  * hipEvents recorded on its own stream.  lac_profile_read synchronises and
  * returns, per kernel id (0 row_stats, 1 encode, 2 finish, 3 decode_step,
  * 4 encode_fused, 5 decode_wave, 6 q1_stats, 7 q1_decode; 8 slots), the summed device milliseconds and the launch
- * count; reset != 0 clears. */
+ * count; reset != 0 clears.  The fused one-position logits step (lac_decode_logits_step /
+ * lac_encode_logits_step) is one launch: its decode reports under 7, its encode under 1,
+ * and 6 gets nothing. */
 int lac_profile_enable(lac_ctx *ctx, int on);
 int lac_profile_read(lac_ctx *ctx, double *ms_total /*[8]*/, int64_t *launches /*[8]*/, int reset);
 

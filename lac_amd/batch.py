@@ -558,6 +558,42 @@ class BatchCoder:
                                                C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    def _logits_step_args(self, logits):
+        typ, _, bs, steps, logits = self._logits_args(logits)
+        if steps != 1:
+            raise ValueError(f"one position: logits must be [{self.streams}, {self.vocab}]")
+        return typ, bs, logits
+
+    def decode_logits_step(self, logits, out=None):
+        """One position of a serving loop: ``logits`` [streams, V] (or [1, streams, V]) ->
+        int32 [1, streams], what :meth:`decode_logits` returns for one step -- in one launch
+        where the job fits (:meth:`set_q1_step`; lac.h lac_decode_logits_step)."""
+        torch = _torch()
+        typ, bs, logits = self._logits_step_args(logits)
+        if out is None:
+            out = torch.empty((1, self.streams), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out(out, 1)
+        check(self.lib.lac_decode_logits_step(self.ctx, C.c_void_p(logits.data_ptr()), typ, bs,
+                                              C.c_void_p(out.data_ptr()), self._stream))
+        return out
+
+    def encode_logits_step(self, logits, sym, trace=None):
+        """One position of a serving loop: :meth:`encode_logits` of one step (``sym``
+        [streams] or [1, streams]) -- in one launch where the job fits (:meth:`set_q1_step`)."""
+        args = self._logits_encode_args(logits, sym, trace)
+        if args[6] != 1:
+            raise ValueError(f"one position: sym must be [{self.streams}]")
+        check(self.lib.lac_encode_logits_step(*args[:3], args[4], args[5], args[7], args[8]))
+
+    def set_q1_step(self, mode):
+        """How the one-position logits calls run (include/lac.h LAC_OPT_Q1_STEP; identical
+        results): "auto" (0) the fused one-launch step where it holds the job, "fused" (1)
+        always -- a job it cannot hold raises LacError (LAC_E_ARG) from the step call --,
+        "split" (2) the two launches of a one-step :meth:`decode_logits` / :meth:`encode_logits`."""
+        v = _lib.Q1_STEP_MODES.get(mode, mode)
+        check(self.lib.lac_set_option(self.ctx, _lib.LAC_OPT_Q1_STEP, int(v)))
+
     def quantize_logits(self, logits):
         """The q1 tables themselves: int32 tensor (uint32 bit patterns) [steps, streams, V]."""
         torch = _torch()

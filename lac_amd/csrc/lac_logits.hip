@@ -4,7 +4,8 @@
 // (and its register + LDS-slot and 8-wave forms k_q1_stats_rl / _wide, row groups)
 // computes each row's RowStats (encode) or maximum and 64 chunk totals (decode);
 // k_q1_decode is the sequential decode over them; k_quantize_logits materialises
-// tables.  DESIGN.md section 5b.
+// tables; k_q1_step_dec / k_q1_step_enc code one position of a few streams in one launch
+// (lac_decode_logits_step / lac_encode_logits_step).  DESIGN.md section 5b.
 #include "lac_host.h"
 #include "lac_dec_dev.h"
 
@@ -1754,6 +1755,332 @@ __global__ __launch_bounds__(256) void k_quantize_logits(const LT *__restrict__ 
     }
 }
 
+// ================================================================ the one-position step
+// k_q1_step_dec / k_q1_step_enc: one position of a model in the loop, one launch.  Workgroup b
+// codes stream b: it loads the row once into registers (R vectors per thread, q1_step_plan's
+// layout: wave w owns the 64 R vectors from w * 64 R, register j of lane l is vector
+// w * 64 R + 64 j + l), takes the maximum, quantises from the registers through one LDS table
+// and scans the sums in entry order -- wave, then register, then lane, then entry --, and
+// wave 0 runs the coder's step.  What the two-launch path passes through memory (the maximum,
+// 64 chunk totals or RowStats) stays in LDS here; the arithmetic of the step itself is that
+// of k_q1_decode / k_encode, so every result is theirs bit for bit.  No workgroup waits on
+// another, and every early exit is uniform and precedes the first barrier.
+#ifndef LAC_Q1_STEP_REP
+#define LAC_Q1_STEP_REP 1        // table copies (power of two <= 32): one row per launch pays the whole fill
+                                 // (8 copies: 9.24 vs 8.94 us per decoded position at one stream,
+                                 // profiles/r07/step/)
+#endif
+constexpr int kStepRep = LAC_Q1_STEP_REP;
+constexpr int kStepWaves = kQ1StepMaxThreads / 64;
+
+struct StepShared {
+    uint32_t tab[LAC_Q1_TAB_SIZE * kStepRep];
+    uint64_t wtot[kStepWaves];                   // wave totals
+    uint64_t jtot[kStepWaves * kQ1StepMaxR];     // decode: a wave's register totals (64 vectors each)
+    uint64_t res[3];                             // decode: s, c_{s-1}, c_s   encode: c_{s-1} in its wave, q_s
+    float wmax[kStepWaves];
+    int found;
+};
+
+// Table fill, row load, maximum (NaN ignored, +-inf kept), quantised sums s[j] of the thread's
+// vectors (0 past the row).  Out-of-row lanes load the row's last vector: a duplicate cannot
+// change the maximum, and the sums mask it afterwards.  One barrier.
+template <typename LT, int R>
+__device__ inline void q1_step_row(const LT *row, int nvec, uint32_t xsh, StepShared &sh, u32x4 (&x)[R],
+                                   uint32_t (&s)[R], float &c) {
+    constexpr int N = LogitN<LT>::N;
+    const int lane = (int)lane_id(), w = wave_in_block(), nw = (int)(blockDim.x >> 6);
+    const int v0 = w * 64 * R + lane;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const int vi = v0 + 64 * j;
+        x[j] = ld16(row, vi < nvec ? vi : nvec - 1, LAC_Q1_NT);
+    }
+    for (int i = threadIdx.x; i < LAC_Q1_TAB_SIZE * kStepRep; i += blockDim.x) sh.tab[i] = q1_entry(i / kStepRep, xsh);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < R; j++)
+#pragma unroll
+        for (int e = 0; e < N; e++) mx = fmaxf(mx, logit_at<LT>(x[j], e));
+    mx = wave_max_f32(mx);
+    if (lane == 0) sh.wmax[w] = mx;
+    // (the sums unpack the vectors again: kept from the maximum's pass, the unpacked bf16 row
+    // is twice the registers and the 16-vector form spilled)
+#pragma unroll
+    for (int j = 0; j < R; j++) asm volatile("" : "+v"(x[j]));
+    __syncthreads();
+    float m = sh.wmax[0];
+    for (int i = 1; i < nw; i++) m = fmaxf(m, sh.wmax[i]);
+    c = q1_c(m);
+    const bool fast = q1_fast_row(m);
+    const uint32_t loff = (uint32_t)(lane & (kStepRep - 1)) * 4u;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const uint32_t q = q1_vec_sum<LT, kStepRep>(x[j], c, fast, sh.tab, loff);
+        s[j] = v0 + 64 * j < nvec ? q : 0u;
+    }
+}
+
+// The inclusive sums of one vector's entries (the general form: on a fast row its cap is idle,
+// so the values are q1_vec_sum's)
+template <typename LT>
+__device__ inline void q1_step_entries(const u32x4 &xv, float c, const uint32_t *tab, uint32_t loff,
+                                       uint32_t (&loc)[LogitN<LT>::N]) {
+    uint32_t ls = 0;
+#pragma unroll
+    for (int e = 0; e < LogitN<LT>::N; e++) {
+        ls += q1_rep_at<kStepRep>(tab, q1_j(logit_at<LT>(xv, e), c), loff);
+        loc[e] = ls;
+    }
+}
+
+template <typename LT, int R, bool SMALL>
+__global__ __launch_bounds__(kQ1StepMaxThreads) void k_q1_step_dec(const LT *__restrict__ lg, int64_t stream_stride,
+                                                                   int64_t V, int prec, uint32_t xsh,
+                                                                   DecState *states, const uint8_t *bits,
+                                                                   uint64_t stride, const uint64_t *nbits,
+                                                                   int32_t *sym_out,
+                                                                   const int64_t *__restrict__ slen) {
+    __shared__ StepShared sh;
+    constexpr int N = LogitN<LT>::N;
+    const int lane = (int)lane_id(), w = wave_in_block(), nw = (int)(blockDim.x >> 6);
+    const int64_t b = blockIdx.x;
+    DecState st = states[b];
+    dec_state_uniform(st);
+    // failed, or at its count (lac_set_stream_lengths): -1, nothing else changes, no row read
+    if (st.err || live_steps(slen, b, st.nsym, 1) == 0) {
+        if (threadIdx.x == 0) sym_out[b] = -1;
+        return;
+    }
+    const int nvec = (int)(V / N);
+    const uint8_t *mybits = bits + b * stride;
+    const uint64_t mynbits = rfl_u64(nbits[b]);
+    BitWin win{0, 0};
+    if (w == 0) win = bit_window(mybits, mynbits, st.pos);     // in flight during the row's work
+    if (threadIdx.x == 0) sh.found = 0;
+    u32x4 x[R];
+    uint32_t s[R];
+    float c;
+    q1_step_row<LT, R>(lg + b * stream_stride, nvec, xsh, sh, x, s, c);
+    // wave totals, and each register's (its 64 vectors') for the search
+    uint32_t ts = 0, sv[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        ts += s[j];                                            // <= 128 entries of <= 2^24
+        sv[j] = s[j];
+    }
+    const uint64_t wt = wave_sum_u64((uint64_t)ts);
+    const uint64_t gsum = wave_multi_sum32<R>(sv);             // lane l < R: register q_index<R>(l)
+    if (lane < R) sh.jtot[w * kQ1StepMaxR + q_index<R>(lane)] = gsum;
+    if (lane == 0) sh.wtot[w] = wt;
+    __syncthreads();
+    uint64_t T = 0, wb = 0;                                    // the row's total, this wave's exclusive prefix
+    for (int i = 0; i < nw; i++) {
+        const uint64_t t = sh.wtot[i];
+        wb += i < w ? t : 0;
+        T += t;
+    }
+    // the targets, as k_q1_decode -- in every wave alike (the state and T are uniform across the
+    // workgroup), so no wave waits for a broadcast; wave 0 keeps them for the step's end
+    int err = 0;
+    uint64_t wd = 0, vh = 0, thi = 0, tgt = 0;
+    {
+        T = rfl_u64(T);
+        const int64_t l = st.l, h = st.h, xx = st.x;
+        if (xx < l || xx > h) err = LAC_E_DECODE_RANGE;
+        wd = (uint64_t)(h - l + 1);
+        const uint64_t v = (uint64_t)(xx - l);
+        if (!err && T > wd) err = LAC_E_TABLE;                 // fudged (minp 1): impossible by the choice of k
+        if (!err) {
+            const uint64_t past = st.pos > mynbits ? st.pos - mynbits : 0;
+            const int u = past < (uint64_t)prec ? (int)past : prec;
+            vh = v + ((1ull << u) - 1);
+            if (SMALL) {
+                const double iw = recip(wd);
+                tgt = div_small_u<false>(v, T, 0, wd, iw);
+                thi = vh == v ? tgt : (vh < wd ? div_small_u<false>(vh, T, 0, wd, iw) : 0);
+            } else {
+                div_pair(v, vh < wd ? vh : 0, T, 0, wd, recip(wd), &tgt, &thi);
+            }
+        }
+    }
+    // the wave whose span holds tgt: its register, then the lane, then the entry
+    if (!err && wb <= tgt && tgt < wb + wt) {
+        uint64_t base = wb;
+        int js = -1;
+#pragma unroll
+        for (int j = 0; j < R; j++) {
+            const uint64_t t = sh.jtot[w * kQ1StepMaxR + j];
+            const bool in = js < 0 && tgt < base + t;
+            js = in ? j : js;
+            base += js < 0 ? t : 0;
+        }
+        js = __builtin_amdgcn_readfirstlane(js);
+        u32x4 xv = x[0];
+        uint32_t sj = s[0];
+#pragma unroll
+        for (int j = 1; j < R; j++)
+            if (j == js) {
+                xv = x[j];
+                sj = s[j];
+            }
+        const uint64_t in = wave_incl_scan_u64((uint64_t)sj);
+        const uint64_t exb = base + in - sj;
+        const uint64_t mk = __ballot(exb + sj > tgt);
+        if (js >= 0 && mk) {
+            const int L = __ffsll((unsigned long long)mk) - 1;
+            // lane L: exb <= tgt < exb + sj, so tgt - exb fits 32 bits there
+            const uint32_t rel = (uint32_t)(tgt - exb);
+            uint32_t loc[N];
+            q1_step_entries<LT>(xv, c, sh.tab, (uint32_t)(lane & (kStepRep - 1)) * 4u, loc);
+            uint32_t k = 0, lo = 0, hi = ~0u;
+#pragma unroll
+            for (int e = 0; e < N; e++) {
+                const bool le = loc[e] <= rel;
+                k += le ? 1u : 0u;
+                lo = le ? loc[e] : lo;
+                hi = (!le && loc[e] < hi) ? loc[e] : hi;
+            }
+            if (lane == L) {
+                sh.res[0] = (uint64_t)(w * 64 * R + 64 * js + L) * N + k;
+                sh.res[1] = exb + lo;
+                sh.res[2] = exb + hi;
+                sh.found = 1;
+            }
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        int64_t sym = -1;
+        if (!err && !sh.found) err = LAC_E_DECODE_RANGE;       // corrupt state: tgt outside the row
+        if (!err) {
+            sym = (int64_t)rfl_u64(sh.res[0]);
+            const uint64_t lo_c = rfl_u64(sh.res[1]), hi_c = rfl_u64(sh.res[2]);
+            uint64_t a, bb;
+            if (SMALL) {
+                div_small_u2<false>(lo_c, hi_c, wd, T - 1, T, recip(T), &a, &bb);
+            } else {
+                div_pair(lo_c, hi_c, wd, T - 1, T, recip(T), &a, &bb);
+            }
+            const bool det = vh < wd && thi < hi_c;
+            if (st.det && det) st.ndet++;
+            else st.det = 0;
+            err = LAC_Q1D_NB ? decode_advance_nb(st, a, bb, win, mynbits, prec)
+                             : decode_advance<true>(st, a, bb, win, mynbits, prec);
+        }
+        if (err) {
+            st.err = err;
+            st.err_step = st.nsym;
+        }
+        if (lane == 0) {
+            states[b] = st;
+            sym_out[b] = err ? -1 : (int32_t)sym;
+        }
+    }
+}
+
+template <typename LT, int R>
+__global__ __launch_bounds__(kQ1StepMaxThreads) void k_q1_step_enc(const LT *__restrict__ lg, int64_t stream_stride,
+                                                                   const int32_t *__restrict__ sym, int64_t V,
+                                                                   int prec, uint32_t xsh,
+                                                                   EncState *states, uint64_t *planeA,
+                                                                   uint64_t *planeC, uint64_t cap_words,
+                                                                   uint64_t *trace,
+                                                                   const int64_t *__restrict__ slen) {
+    __shared__ StepShared sh;
+    constexpr int N = LogitN<LT>::N;
+    const int lane = (int)lane_id(), w = wave_in_block(), nw = (int)(blockDim.x >> 6);
+    const int64_t b = blockIdx.x;
+    EncState st = states[b];
+    // as k_encode: an ended stream (lac_set_stream_lengths) changes nothing and raises nothing;
+    // a failed one stays as it is; a finished one fails with LAC_E_STATE
+    if (live_steps(slen, b, st.nsym, 1) == 0) return;
+    if (st.err || st.nflush >= 0) {
+        if (threadIdx.x == 0 && !st.err && st.nflush >= 0) {
+            st.err = LAC_E_STATE;
+            st.err_step = st.nsym;
+            states[b] = st;
+        }
+        return;
+    }
+    const int nvec = (int)(V / N);
+    // the symbol's place in the row, of a symbol clamped into it: an out-of-range one reads
+    // nothing out of bounds and fails in coder_step
+    const int32_t s0 = __builtin_amdgcn_readfirstlane(sym[b]);
+    const int sc = (uint32_t)s0 < (uint32_t)V ? s0 : 0;
+    const int vs = sc / N, es = sc % N, ws = vs / (64 * R), js = (vs / 64) % R, ls = vs % 64;
+    u32x4 x[R];
+    uint32_t s[R];
+    float c;
+    q1_step_row<LT, R>(lg + b * stream_stride, nvec, xsh, sh, x, s, c);
+    uint32_t ts = 0;
+#pragma unroll
+    for (int j = 0; j < R; j++) ts += s[j];                    // <= 128 entries of <= 2^24
+    const uint64_t wt = wave_sum_u64((uint64_t)ts);
+    if (lane == 0) sh.wtot[w] = wt;
+    if (w == ws) {
+        // everything of this wave below the symbol's vector, then the vector's entries below it
+        uint32_t cl = 0, sj = s[0];
+        u32x4 xv = x[0];
+#pragma unroll
+        for (int j = 0; j < R; j++) {
+            cl += j < js ? s[j] : 0u;
+            if (j == js) {
+                xv = x[j];
+                sj = s[j];
+            }
+        }
+        cl += lane < ls ? sj : 0u;
+        const uint64_t pre = wave_sum_u64((uint64_t)cl);
+        uint32_t loc[N];
+        q1_step_entries<LT>(xv, c, sh.tab, (uint32_t)(lane & (kStepRep - 1)) * 4u, loc);
+        uint32_t below = 0, upto = loc[0];
+#pragma unroll
+        for (int e = 1; e < N; e++) {
+            below = e == es ? loc[e - 1] : below;
+            upto = e == es ? loc[e] : upto;
+        }
+        if (lane == ls) {
+            sh.res[0] = pre + below;
+            sh.res[1] = (uint64_t)(upto - below);
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    uint64_t T = 0, lo = sh.res[0];
+    for (int i = 0; i < nw; i++) {
+        const uint64_t t = sh.wtot[i];
+        lo += i < ws ? t : 0;
+        T += t;
+    }
+    T = rfl_u64(T);
+    lo = rfl_u64(lo);
+    const uint64_t hi = lo + rfl_u64(sh.res[1]);
+    // k_encode's general step over the RowStats the q1 statistics kernels write: {lo, hi, T,
+    // minp 1, 1 / T}, no fudging
+    uint64_t *pa = planeA + (uint64_t)b * cap_words, *pc = planeC + (uint64_t)b * cap_words;
+    int64_t l = (int64_t)rfl_u64((uint64_t)st.l), h = (int64_t)rfl_u64((uint64_t)st.h);
+    st.L = rfl_u64(st.L);
+    st.wa = rfl_u64(st.wa);
+    st.wc = rfl_u64(st.wc);
+    st.nsym = (int64_t)rfl_u64((uint64_t)st.nsym);
+    int64_t err_step0 = st.err_step;
+    // (no row fractions: k_encode computes 64 steps' worth at once, off its chain; for one step
+    // coder_step's own division of both ends, lanes 0 and 1, is shorter -- the quotients are exact
+    // either way)
+    const uint64_t fthr = T < (1ull << 62) ? T : (1ull << 62);  // ceil(T / minp), minp = 1
+    const double inv = 1.0 / (double)T;
+    coder_step<uint32_t, true>(st, l, h, lo, hi, T, 1, (int64_t)s0, (const uint32_t *)nullptr, V, prec, pa, pc,
+                               cap_words, trace ? trace + 2 * b : nullptr, lane, LAC_MAP_CEIL, inv, false, kNoFrac,
+                               kNoFrac, fthr);
+    // (the loaded err_step handed to store_state through an opaque register: merged across
+    // coder_step's scalar branches, the compiler kept the failing paths' value -- nsym -- on the
+    // path that appends digits and succeeds)
+    asm volatile("" : "+v"(err_step0));
+    st.err_step = err_step0;
+    if (lane == 0) store_state(st, l, h, pa, pc, cap_words, &states[b]);
+}
+
 
 }  // namespace
 
@@ -1965,8 +2292,92 @@ static int q1_decode(lac_ctx *c, const Q1Args &a0, int64_t steps, int32_t *out, 
     return LAC_OK;
 }
 
+// The fused one-position step in the plan's shape (q1_step_plan, lac_select.h): one launch, one
+// workgroup per stream.
+template <typename LT>
+static int q1_step_decode(lac_ctx *c, const Q1Args &a, const Q1StepPlan &p, int32_t *out, hipStream_t st) {
+    ProfScope ps(c, KID_Q1_DECODE, st);
+#define LAC_Q1_STEP_DEC(R, SMALL)                                                                               \
+    k_q1_step_dec<LT, R, SMALL><<<(unsigned)c->B, p.threads, 0, st>>>((const LT *)a.lg, a.bs, c->V, c->prec, a.xsh, \
+                                                                      c->dec, c->dbits, c->dstride, c->dnbits, out, \
+                                                                      stream_lengths(c))
+    // prec > 50 (quotients past div_small's range): the general form, as q1_decode
+    if (c->prec > 50) {
+        if (p.R == 4) LAC_Q1_STEP_DEC(4, false);
+        else if (p.R == 8) LAC_Q1_STEP_DEC(8, false);
+        else LAC_Q1_STEP_DEC(16, false);
+    } else {
+        if (p.R == 4) LAC_Q1_STEP_DEC(4, true);
+        else if (p.R == 8) LAC_Q1_STEP_DEC(8, true);
+        else LAC_Q1_STEP_DEC(16, true);
+    }
+#undef LAC_Q1_STEP_DEC
+    CHECK_LAUNCH();
+    return LAC_OK;
+}
+
+template <typename LT>
+static int q1_step_encode(lac_ctx *c, const Q1Args &a, const Q1StepPlan &p, uint64_t *trace, hipStream_t st) {
+    ProfScope ps(c, KID_ENCODE, st);
+#define LAC_Q1_STEP_ENC(R)                                                                                        \
+    k_q1_step_enc<LT, R><<<(unsigned)c->B, p.threads, 0, st>>>((const LT *)a.lg, a.bs, a.sym, c->V, c->prec, a.xsh, \
+                                                               c->enc, c->planeA, c->planeC, c->cap_words, trace,   \
+                                                               stream_lengths(c))
+    if (p.R == 4) LAC_Q1_STEP_ENC(4);
+    else if (p.R == 8) LAC_Q1_STEP_ENC(8);
+    else LAC_Q1_STEP_ENC(16);
+#undef LAC_Q1_STEP_ENC
+    CHECK_LAUNCH();
+    return LAC_OK;
+}
+
+// LAC_OPT_Q1_STEP's choice for this context's job
+static int q1_step_choose(lac_ctx *c, int logit_type, Q1StepPlan *p) {
+    *p = q1_step_plan(c->cus, c->V, logit_type == LAC_LOGITS_BF16 ? 2 : 4, c->B, c->q1_step);
+    if (p->rc)
+        return fail(p->rc, "the fused logits step holds rows of <= %d vectors for <= %lld streams", kQ1StepMaxVec,
+                    (long long)(kQ1StepMaxStreams < c->cus ? kQ1StepMaxStreams : c->cus));
+    return LAC_OK;
+}
 
 extern "C" {
+
+int lac_decode_logits_step(lac_ctx *c, const void *logits_dev, int logit_type, int64_t stream_stride,
+                           int32_t *sym_out_dev, void *stream) {
+    if (!c || !logits_dev || !sym_out_dev) return fail(LAC_E_ARG, "NULL argument");
+    if (c->mode != 1) return fail(LAC_E_STATE, "call lac_decode_open first");
+    int rc = logits_check(c, logits_dev, logit_type, 0, stream_stride, 1);
+    uint32_t xsh = 0;
+    Q1StepPlan p;
+    if (rc || (rc = q1_shift(c, &xsh)) || (rc = q1_step_choose(c, logit_type, &p))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const Q1Args a{logits_dev, 0, stream_stride, nullptr, 0, 0, xsh};
+    if (!p.fused)                                                // the two launches of the steps = 1 call
+        return logit_type == LAC_LOGITS_BF16 ? q1_decode<uint16_t>(c, a, 1, sym_out_dev, S(stream))
+                                             : q1_decode<float>(c, a, 1, sym_out_dev, S(stream));
+    return logit_type == LAC_LOGITS_BF16 ? q1_step_decode<uint16_t>(c, a, p, sym_out_dev, S(stream))
+                                         : q1_step_decode<float>(c, a, p, sym_out_dev, S(stream));
+}
+
+int lac_encode_logits_step(lac_ctx *c, const void *logits_dev, int logit_type, int64_t stream_stride,
+                           const int32_t *sym_dev, uint64_t *trace_dev, void *stream) {
+    if (!c || !logits_dev || !sym_dev) return fail(LAC_E_ARG, "NULL argument");
+    int rc = logits_check(c, logits_dev, logit_type, 0, stream_stride, 1);
+    uint32_t xsh = 0;
+    Q1StepPlan p;
+    if (rc || (rc = q1_shift(c, &xsh)) || (rc = q1_step_choose(c, logit_type, &p))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    c->mode = 0;
+    const Q1Args a{logits_dev, 0, stream_stride, sym_dev, 0, 0, xsh};
+    if (!p.fused)
+        rc = logit_type == LAC_LOGITS_BF16 ? q1_encode<uint16_t>(c, a, 1, trace_dev, S(stream), 0)
+                                           : q1_encode<float>(c, a, 1, trace_dev, S(stream), 0);
+    else
+        rc = logit_type == LAC_LOGITS_BF16 ? q1_step_encode<uint16_t>(c, a, p, trace_dev, S(stream))
+                                           : q1_step_encode<float>(c, a, p, trace_dev, S(stream));
+    if (rc == LAC_OK) enc_mark_open(c);
+    return rc;
+}
 
 static int logits_encode(lac_ctx *c, const void *logits_dev, int logit_type, int64_t step_stride,
                          int64_t stream_stride, const int32_t *sym_dev, int64_t steps, uint64_t *trace_dev,

@@ -249,9 +249,52 @@ inline int q1_plan(int cus, int64_t V, int type_bytes, bool dec, int forced_shap
     return LAC_OK;
 }
 
+// ============================================================ logits one-position step (q1)
+// k_q1_step_dec / k_q1_step_enc (lac_logits.hip): one workgroup per stream codes one position
+// in one launch, the row held once in registers -- R 16-B vectors per thread of a block of up
+// to 16 waves, wave w owning the R * 64 consecutive vectors from w * 64 * R (register j of lane l:
+// vector w * 64 * R + 64 j + l, so every load instruction of a wave reads 1 KB in a piece).
+constexpr int kQ1StepMaxThreads = 1024;
+constexpr int kQ1StepMaxR = 16;
+constexpr int kQ1StepMaxVec = kQ1StepMaxThreads * kQ1StepMaxR;   // 16384: bf16 V <= 131072, f32 V <= 65536
+// AUTO takes the fused step up to this many streams, beyond them the two-launch path (row
+// statistics + k_q1_decode / k_encode): one resident workgroup per compute unit at most.
+// Measured on MI355X at V = 32000 bf16 (profiles/r07/step/, us per position, fused / two
+// launches): decode 8.94 / 12.02 at 1 stream, 9.15 / 11.96 at 4, 9.60 / 12.79 at 16, 9.52 /
+// 12.76 at 64, 10.47 / 12.56 at 256; encode 9.09 / 12.14 .. 9.87 / 14.59 -- the fused step
+// wins at every measured count up to one workgroup per CU, so the cap is the CU count.
+#ifndef LAC_Q1_STEP_MAX_STREAMS
+#define LAC_Q1_STEP_MAX_STREAMS 256
+#endif
+constexpr int64_t kQ1StepMaxStreams = LAC_Q1_STEP_MAX_STREAMS;
+enum { Q1_STEP_AUTO = 0, Q1_STEP_FUSED = 1, Q1_STEP_SPLIT = 2 };   // LAC_OPT_Q1_STEP
+struct Q1StepPlan {
+    bool fused = false;
+    int rc = LAC_OK;                 // LAC_E_ARG: mode 1 on a shape the fused step cannot take
+    int threads = 0, R = 0;          // the block, and 16-B vectors per thread (4, 8 or 16)
+};
+// The fewest vectors per thread whose full block holds the row (the most threads share the
+// row: at one stream nothing else hides the loads' latency), then the fewest whole waves.
+inline Q1StepPlan q1_step_plan(int cus, int64_t V, int type_bytes, int64_t streams, int mode) {
+    Q1StepPlan p;
+    const int64_t nvec = V / (type_bytes == 2 ? 8 : 4);
+    const int64_t cap = kQ1StepMaxStreams < cus ? kQ1StepMaxStreams : cus;
+    const bool fits = nvec >= 1 && nvec <= kQ1StepMaxVec && streams >= 1 && streams <= cap;
+    if (mode == Q1_STEP_SPLIT) return p;
+    if (!fits) {
+        if (mode == Q1_STEP_FUSED) p.rc = LAC_E_ARG;
+        return p;
+    }
+    p.fused = true;
+    p.R = nvec <= 4 * kQ1StepMaxThreads ? 4 : nvec <= 8 * kQ1StepMaxThreads ? 8 : 16;
+    const int64_t thr = ((nvec + p.R - 1) / p.R + 63) / 64 * 64;
+    p.threads = (int)(thr < kQ1StepMaxThreads ? thr : kQ1StepMaxThreads);
+    return p;
+}
+
 // ================================================================== pmf decode path
 #ifndef LAC_LEAN
-#define LAC_LEAN 1          // few-stream decode: k_decode_lean ahead of k_decode_seq (probe builds set 0)
+#define LAC_LEAN 1         // few-stream decode: k_decode_lean ahead of k_decode_seq (probe builds set 0)
 #endif
 #ifndef LAC_LEAN_HELP
 #define LAC_LEAN_HELP 1     // k_decode_lean: L2-prefetching helper workgroups for <= 16 streams

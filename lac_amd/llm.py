@@ -234,8 +234,8 @@ class LogitsCompressor:
     bit-identical logits, so both sides produce them the same way:
 
     * incremental (a module with ``init_cache`` / ``step``, e.g. TinyCausalLM):
-      one cached step per position on both sides (``encode_logits`` /
-      ``decode_logits`` per step) -- O(T) steps each way, as a serving loop;
+      one cached step per position on both sides (``encode_logits_step`` /
+      ``decode_logits_step`` per position) -- O(T) steps each way, as a serving loop;
     * otherwise (``module(tokens[B, T]) -> logits[B, T, V]`` only): compress runs
       one teacher-forced forward, and decompress re-runs the *same* fixed-shape
       [B, T] forward (not-yet-decoded positions 0) before each step -- under the
@@ -243,13 +243,14 @@ class LogitsCompressor:
       the same kernels.  O(T) full forwards: for modules without a cache.
     """
 
-    def __init__(self, module, vocab, prec=48, bos=1, logits_dtype=None, device="cuda"):
+    def __init__(self, module, vocab, prec=48, bos=1, logits_dtype=None, device="cuda", q1_step="auto"):
         import torch
         from .batch import logits_row_multiple
         self.module = module.to(device).eval()
         self.vocab, self.prec, self.bos = int(vocab), int(prec), int(bos)
         self.dtype = logits_dtype or torch.bfloat16
         self.device = torch.device(device)
+        self.q1_step = q1_step            # BatchCoder.set_q1_step: how the per-position calls run
         self.incremental = hasattr(module, "step") and hasattr(module, "init_cache")
         # the logits kernels read rows as 16-B vectors: a vocab that is not a multiple
         # of 8 (bf16) / 4 (f32) -- GPT-2's 50257, say -- is coded over rows padded
@@ -292,8 +293,10 @@ class LogitsCompressor:
 
     def _coder(self, B, T):
         from .batch import BatchCoder
-        return BatchCoder(self.vcode, B, prec=self.prec, pmf_bits=32, capacity_bits=T * (self.prec + 2) + 256,
-                          device=self.device)
+        coder = BatchCoder(self.vcode, B, prec=self.prec, pmf_bits=32, capacity_bits=T * (self.prec + 2) + 256,
+                           device=self.device)
+        coder.set_q1_step(self.q1_step)
+        return coder
 
     def _lengths(self, lengths, B, T):
         n = np.asarray(lengths.detach().cpu().numpy() if hasattr(lengths, "detach") else lengths)
@@ -320,7 +323,7 @@ class LogitsCompressor:
             sym = tokens.t().contiguous().to(torch.int32)          # [T, B]
             coder.reset()
             for t, lg in self._steps(B, T, lambda t: tokens[:, t]):
-                coder.encode_logits(lg, sym[t:t + 1])
+                coder.encode_logits_step(lg, sym[t:t + 1])
             coder.finish()
         else:
             coder.encode_logits_job(self.logits(tokens).transpose(0, 1), tokens.t().contiguous().to(torch.int32))
@@ -350,7 +353,7 @@ class LogitsCompressor:
         fed = (lambda s: torch.where(s < 0, torch.full_like(s, self.bos), s)) if lengths is not None else (lambda s: s)
         if self.incremental:
             for t, lg in self._steps(B, T, lambda t: fed(out[:, t])):
-                out[:, t] = coder.decode_logits(lg)[0].to(torch.long)
+                out[:, t] = coder.decode_logits_step(lg)[0].to(torch.long)
         else:
             ctx = torch.zeros((B, T), dtype=torch.long, device=self.device)
             ctx[:, 0] = self.bos

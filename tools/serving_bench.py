@@ -5,23 +5,30 @@ position t's symbol before the model can run step t+1, so the coder sits between
 model steps at every position.
 
     python tools/serving_bench.py --streams 1 --positions 256 [--model tiny|small] [--out F]
+        [--step auto|fused|split|ab] [--dtype bf16|f32] [--coder-only] [--repeats N]
 
 Per position t, ``LogitsCompressor.decompress`` (lac_amd/llm.py) runs one cached model
 step (TinyCausalLM, random init: no checkpoint can be fetched) to bf16 logits [1, B,
-V=32000] in HBM, then ``BatchCoder.decode_logits`` -- k_q1_stats (row statistics of the
-q1 tables, computed in-kernel) + k_q1_decode (the per-stream chain) -- whose symbols feed
-the next step on the device (no host round trip).  Reported, in microseconds per
-position (wall clock over the whole loop, one synchronisation at its end, after a warm
+V=32000] in HBM, then ``BatchCoder.decode_logits_step`` -- with ``--step split`` k_q1_stats
+(row statistics of the q1 tables, computed in-kernel) + k_q1_decode (the per-stream chain),
+with ``--step fused`` the one-launch k_q1_step_dec, with ``auto`` (default) the library's
+choice (LAC_OPT_Q1_STEP); ``ab`` times ``coder_only`` in both modes, alternating -- whose
+symbols feed the next step on the device (no host round trip).  Reported, in microseconds
+per position (wall clock over the whole loop, one synchronisation at its end, after a warm
 run of the same loop):
 
 * ``decompress``: the serving loop itself (model + coder, as a user runs it);
 * ``model_only``: the same loop with the tokens known and no coder;
-* ``coder_only``: decode_logits over the same logits, resident in HBM, position by
-  position (launches included);
+* ``coder_only``: decode_logits_step over the same logits, resident in HBM, position by
+  position (launches included); ``--repeats N`` times the loop N times after the warm run
+  and records every repeat beside the best;
 * ``coder_device``: the coder's kernels' device time per position (hipEvents of liblac
   on the coder's stream, lac_profile_*), split into k_q1_stats and k_q1_decode;
-* the same three for compress (encode_logits per position);
+* the same three for compress (encode_logits_step per position);
 * ``coder_share`` = coder_only / decompress.
+
+``--coder-only`` skips the serving loops and the model-only loop (one pass of the model makes
+the logits; the coder's own encode makes the bits to decode).
 
 Bits are checked: decompress returns the tokens compress coded.  Prints one JSON line.
 """
@@ -47,6 +54,10 @@ def main():
     ap.add_argument("--vocab", type=int, default=32000)
     ap.add_argument("--model", choices=sorted(MODELS), default="tiny")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--step", choices=("auto", "fused", "split", "ab"), default="auto")
+    ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
+    ap.add_argument("--coder-only", action="store_true")
+    ap.add_argument("--repeats", type=int, default=1)
     a = ap.parse_args()
     import torch
     from lac_amd.llm import LogitsCompressor, TinyCausalLM
@@ -54,7 +65,9 @@ def main():
     B, T, V = a.streams, a.positions, a.vocab
     cfg = MODELS[a.model]
     model = TinyCausalLM(vocab=V, max_len=max(T, 16), seed=7, **cfg).to(dev).eval()
-    lc = LogitsCompressor(model, V, prec=48, logits_dtype=torch.bfloat16, device=dev)
+    dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    lc = LogitsCompressor(model, V, prec=48, logits_dtype=dtype, device=dev,
+                          q1_step="auto" if a.step == "ab" else a.step)
     g = torch.Generator(device=dev).manual_seed(11)
     tokens = torch.randint(0, V, (B, T), generator=g, device=dev)
     sync = torch.cuda.synchronize
@@ -71,9 +84,12 @@ def main():
         return best, r
 
     # ---- the serving loops (model + coder)
-    t_comp, (data, nbits) = timed(lambda: lc.compress(tokens))
-    t_dec, got = timed(lambda: lc.decompress(data, nbits, T))
-    ok = bool(torch.equal(got.cpu(), tokens.cpu()))
+    t_comp = t_dec = t_model = None
+    ok = True
+    if not a.coder_only:
+        t_comp, (data, nbits) = timed(lambda: lc.compress(tokens))
+        t_dec, got = timed(lambda: lc.decompress(data, nbits, T))
+        ok = bool(torch.equal(got.cpu(), tokens.cpu()))
 
     # ---- the model alone: the same cached steps, tokens known
     def model_only():
@@ -81,12 +97,19 @@ def main():
         for _, lg in lc._steps(B, T, lambda t: tokens[:, t]):
             last = lg
         return last
-    t_model, _ = timed(model_only)
+    if not a.coder_only:
+        t_model, _ = timed(model_only)
 
     # ---- the coder alone over resident logits, position by position
     logits = [lg.clone() for _, lg in lc._steps(B, T, lambda t: tokens[:, t])]
     sym = tokens.t().contiguous().to(torch.int32)
     coder = lc._coder(B, T)
+    if a.coder_only:                                       # the bits to decode: the coder's own
+        coder.reset()
+        for t in range(T):
+            coder.encode_logits_step(logits[t], sym[t:t + 1])
+        coder.finish()
+        data, nbits = coder.to_bytes()
     buf_stride = max(8, (max(len(d) for d in data) + 8) // 8 * 8)
     import numpy as np
     host = np.zeros((B, buf_stride), dtype=np.uint8)
@@ -99,19 +122,33 @@ def main():
     def coder_decode():
         coder.decode_open(dbits, dnb)
         for t in range(T):
-            coder.decode_logits(logits[t], out=out[t:t + 1])
+            coder.decode_logits_step(logits[t], out=out[t:t + 1])
         return out
 
     def coder_encode():
         coder.reset()
         for t in range(T):
-            coder.encode_logits(logits[t], sym[t:t + 1])
+            coder.encode_logits_step(logits[t], sym[t:t + 1])
         coder.finish()
-    t_cdec, _ = timed(coder_decode)
-    dec_ok = bool(torch.equal(out, sym))
-    t_cenc, _ = timed(coder_encode)
-    enc_bytes, enc_nb = coder.to_bytes()
-    enc_ok = all(enc_bytes[b] == data[b] for b in range(B))
+    # --step ab: both modes on the same coder and logits, alternating repeat by repeat (a warm
+    # run of each first), so drift of clocks or of the machine's load falls on both alike
+    modes = ["fused", "split"] if a.step == "ab" else [a.step]
+    reps = {m: {"dec": [], "enc": []} for m in modes}
+    dec_ok = enc_ok = True
+    for r in range(1 + max(1, a.repeats)):
+        for m in modes:
+            coder.set_q1_step(m)
+            out.fill_(-2)
+            dt, _ = timed(coder_decode, 1)
+            dec_ok = dec_ok and bool(torch.equal(out, sym))
+            et, _ = timed(coder_encode, 1)
+            enc_bytes, enc_nb = coder.to_bytes()
+            enc_ok = enc_ok and all(enc_bytes[b] == data[b] for b in range(B))
+            if r > 0:
+                reps[m]["dec"].append(dt)
+                reps[m]["enc"].append(et)
+    t_cdec, t_cenc = min(reps[modes[0]]["dec"]), min(reps[modes[0]]["enc"])
+    r_cdec, r_cenc = reps[modes[0]]["dec"], reps[modes[0]]["enc"]
 
     # ---- device time of the coder's kernels (liblac's hipEvents on its stream)
     def device_ms(fn):
@@ -125,25 +162,39 @@ def main():
         coder.lib.lac_profile_read(coder.ctx, C.cast(ms, C.c_void_p), C.cast(cnt, C.c_void_p), 1)
         return {k: (ms[i] * 1e3 / T, int(cnt[i])) for k, i in
                 (("row_stats", 0), ("encode", 1), ("finish", 2), ("q1_stats", 6), ("q1_decode", 7)) if cnt[i]}
-    ddec = device_ms(coder_decode)
-    denc = device_ms(coder_encode)
+    dev_us = {}
+    for m in modes:
+        coder.set_q1_step(m)
+        dev_us[m] = (device_ms(coder_decode), device_ms(coder_encode))
+    ddec, denc = dev_us[modes[0]]
     coder.close()
 
-    us = lambda s: 1e6 * s / T                               # noqa: E731
+    us = lambda s: None if s is None else 1e6 * s / T        # noqa: E731
     res = {
-        "what": "coder cost per position in the ROCm serving loop (LogitsCompressor, bf16 logits)",
+        "what": f"coder cost per position in the ROCm serving loop (LogitsCompressor, {a.dtype} logits)",
+        "step": a.step, "dtype": a.dtype,
         "model": f"TinyCausalLM {cfg} (random init), cached step per position",
         "vocab": V, "streams": B, "positions": T, "prec": 48,
         "roundtrip_ok": ok and dec_ok and enc_ok,
         "decompress_us_per_pos": us(t_dec), "compress_us_per_pos": us(t_comp),
         "model_only_us_per_pos": us(t_model),
         "coder_decode_only_us_per_pos": us(t_cdec), "coder_encode_only_us_per_pos": us(t_cenc),
+        "coder_decode_only_repeats_us": [round(us(v), 3) for v in r_cdec],
+        "coder_encode_only_repeats_us": [round(us(v), 3) for v in r_cenc],
         "coder_decode_device_us_per_pos": {k: round(v[0], 3) for k, v in ddec.items()},
         "coder_encode_device_us_per_pos": {k: round(v[0], 3) for k, v in denc.items()},
-        "coder_share_of_decompress": t_cdec / t_dec,
-        "coder_share_of_compress": t_cenc / t_comp,
-        "logits_bytes_per_pos": B * lc.vcode * 2,
+        "coder_share_of_decompress": None if t_dec is None else t_cdec / t_dec,
+        "coder_share_of_compress": None if t_comp is None else t_cenc / t_comp,
+        "logits_bytes_per_pos": B * lc.vcode * (2 if a.dtype == "bf16" else 4),
     }
+    if a.step == "ab":                                     # (the keys above: the first mode, fused)
+        res["by_mode"] = {m: {
+            "coder_decode_only_us_per_pos": us(min(reps[m]["dec"])), "coder_encode_only_us_per_pos": us(min(reps[m]["enc"])),
+            "coder_decode_only_repeats_us": [round(us(v), 3) for v in reps[m]["dec"]],
+            "coder_encode_only_repeats_us": [round(us(v), 3) for v in reps[m]["enc"]],
+            "coder_decode_device_us_per_pos": {k: round(v[0], 3) for k, v in dev_us[m][0].items()},
+            "coder_encode_device_us_per_pos": {k: round(v[0], 3) for k, v in dev_us[m][1].items()},
+        } for m in modes}
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
