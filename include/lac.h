@@ -222,6 +222,35 @@ int lac_encode_job(lac_ctx *ctx, const void *pmf_dev, int64_t step_stride, int64
  * Asynchronous on `stream`. */
 int lac_encode_rebase(lac_ctx *ctx, void *stream);
 
+/* Drain settled output mid-job, so that capacity_bits bounds the bits coded between two drains
+ * and not the stream: each stream's settled prefix -- whole 64-bit words, resolved to their final
+ * bytes -- is appended to the caller's slot b at dst_dev + b * dst_stride_bytes + fill_dev[b],
+ * fill_dev[b] (uint64 [streams], in/out: bytes already in each slot) grows by the 8 g bytes
+ * written, and the stream goes on coding in the words that remain (L shrinks by 64 g).  One
+ * launch (k_enc_drain, one wave per stream) that reads only the words a stream holds;
+ * asynchronous on `stream`, no host synchronisation, no allocation.  Every encode call, the
+ * logits calls, lac_encode_get_state / set_state (they describe the remaining words with the
+ * smaller L) and lac_set_output buffers work on the drained context as on any other.
+ *   What a drain holds back (lac_amd/csrc/lac_drain.h):
+ *   1. without a certain state, everything from the last word below the active one whose resolved
+ *      value is neither 0 nor 2^64 - 1 (the guard word: a later carry of +-1 cannot pass it);
+ *   2. in a certain state (0 <= l and h < 2^prec: no later digit carries) only the active word.
+ *   The kept first word is stored resolved (plane C zero).
+ * Contract, per stream: the bytes drained over all calls followed by the bytes of the final
+ * lac_encode_finish are the bytes of the same symbols coded with no drain, and 8 * (drained
+ * bytes) + nbits is that job's bit count.  The caller owns the drained bytes and their count:
+ * they are no part of lac_enc_state, and lac_encode_reset does not touch fill_dev.  Registers,
+ * nsym, status and err_step, traces, lac_flush_digits and per-stream counts mean what they did.
+ *   All or nothing per stream: a stream whose 8 g bytes do not fit dst_stride_bytes - fill_dev[b]
+ *   (or whose fill_dev[b] is no multiple of 8) drains nothing and changes nothing -- not an error;
+ *   a later call with room takes it.  No byte at or past dst_stride_bytes of a slot is written.
+ *   A stream with a sticky error, a finished stream and one of at most 64 bits do nothing.
+ * Refused before anything is launched, nothing changed: LAC_E_STATE while a decode is open, or
+ * after lac_encode_finish / a job with no lac_encode_reset since (plane A holds packed bytes
+ * then); LAC_E_ARG for a NULL dst_dev or fill_dev, or dst_dev, fill_dev or dst_stride_bytes not
+ * a multiple of 8. */
+int lac_encode_drain(lac_ctx *ctx, uint8_t *dst_dev, uint64_t dst_stride_bytes, uint64_t *fill_dev, void *stream);
+
 /* Flush every stream and resolve carries into packed bytes (asynchronous). */
 int lac_encode_finish(lac_ctx *ctx, void *stream);
 

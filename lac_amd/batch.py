@@ -206,6 +206,31 @@ class BatchCoder:
         ``trace`` and only need the coder state to continue."""
         check(self.lib.lac_encode_rebase(self.ctx, self._stream))
 
+    def drain(self, out, fill):
+        """Move every stream's settled output, as final bytes, behind the ``fill[b]`` bytes of
+        row b of ``out`` and keep coding in the words that remain (include/lac.h
+        lac_encode_drain): capacity then bounds the bits coded between two drains, not the
+        stream.  ``out``: a contiguous uint8 device tensor [streams, stride], 8-byte aligned,
+        stride a multiple of 8 (row b is stream b's slot); ``fill``: a contiguous int64/uint64 device tensor
+        [streams], bytes already in each row, grown by what is written.  A stream whose settled
+        bytes do not fit its row drains nothing.  The drained bytes followed by the bytes of the
+        final :meth:`finish` are the undrained stream.  Asynchronous; no host sync."""
+        torch = _torch()
+        if out.dtype != torch.uint8 or out.device != self.device:
+            raise TypeError("out must be a uint8 tensor on the coder's device")
+        if out.dim() != 2 or out.shape[0] != self.streams or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [streams, stride] tensor (a row is a slot)")
+        stride = out.shape[1]
+        if stride % 8 or out.data_ptr() % 8:
+            raise ValueError("out rows must be 8-byte aligned (row length a multiple of 8 bytes)")
+        if fill.dtype not in (torch.int64, torch.uint64) or fill.device != self.device:
+            raise TypeError("fill must be an int64/uint64 tensor on the coder's device")
+        if tuple(fill.shape) != (self.streams,) or not fill.is_contiguous():
+            raise ValueError(f"fill must be a contiguous [{self.streams}] tensor")
+        self._drain_keep = (out, fill)
+        check(self.lib.lac_encode_drain(self.ctx, C.c_void_p(out.data_ptr()), stride,
+                                        C.c_void_p(fill.data_ptr()), self._stream))
+
     def status(self):
         err = np.zeros(self.streams, dtype=np.int32)
         step = np.zeros(self.streams, dtype=np.int64)
@@ -616,6 +641,51 @@ class BatchCoder:
     def q1_k(self):
         """The q1 table scale: max entry 2^k, k = min(24, prec - 1 - ceil(log2 V)) (lac.h lac_q1_k)."""
         return int(self.lib.lac_q1_k(self.prec, self.vocab))
+
+
+class DrainSink:
+    """Streams longer than the coder's capacity: collects what :meth:`BatchCoder.drain` hands
+    out.  Owns a device staging tensor [streams, stage_bytes] (one coder capacity wide by
+    default, so a drain always fits after a pull) and its ``fill`` counts.
+
+        sink = DrainSink(coder)
+        for t in range(T):
+            coder.encode(pmf[t:t + 1], sym[t:t + 1])
+            if (t + 1) % 64 == 0:
+                sink.pull()
+        data, nbits = sink.finish()              # what to_bytes() returns for the whole streams
+    """
+
+    def __init__(self, coder: BatchCoder, stage_bytes: int | None = None):
+        torch = _torch()
+        self.coder = coder
+        self.stage_bytes = int(stage_bytes if stage_bytes is not None else coder.bits_stride())
+        if self.stage_bytes <= 0 or self.stage_bytes % 8:
+            raise ValueError("stage_bytes must be a positive multiple of 8")
+        self.stage = torch.zeros((coder.streams, self.stage_bytes), dtype=torch.uint8, device=coder.device)
+        self.fill = torch.zeros((coder.streams,), dtype=torch.int64, device=coder.device)
+        self.parts = [bytearray() for _ in range(coder.streams)]
+
+    def pull(self):
+        """Drain, copy the bytes drained to the per-stream host ``bytearray``s (``parts``) and
+        empty the staging rows.  Synchronises (the copy to the host)."""
+        self.coder.drain(self.stage, self.fill)
+        n = self.fill.cpu().numpy()
+        if n.any():
+            host = self.stage[:, :int(n.max())].cpu().numpy()
+            for b in np.flatnonzero(n):
+                self.parts[b] += host[b, :int(n[b])].tobytes()
+            self.fill.zero_()
+        return n
+
+    def finish(self):
+        """pull, finish the coder -> (list of per-stream bytes, nbits uint64 [streams]) of the
+        whole streams: the drained bytes followed by the finished tail."""
+        self.pull()
+        self.coder.finish()
+        tail, nb = self.coder.to_bytes()
+        drained = np.array([len(p) for p in self.parts], dtype=np.uint64)
+        return [bytes(p) + t for p, t in zip(self.parts, tail)], nb + 8 * drained
 
 
 def logits_row_multiple(dtype) -> int:

@@ -7,7 +7,8 @@
 //
 // Kernels by file:
 //   lac_encode.hip  k_row_stats + k_encode (split path), k_encode_fused, k_finish,
-//                   k_pack (the gather's packing), k_unpack (its inverse), reset / rebase
+//                   k_pack (the gather's packing), k_unpack (its inverse), reset / rebase,
+//                   k_enc_drain (settled output out mid-job, lac_drain.h)
 //   lac_decode.hip  k_decode_wave(_fine), k_decode_block, k_dec_stats + k_decode_seq,
 //                   k_decode_lean, k_decode_step, the reference-frame tail (lac_tail.h)
 //   lac_logits.hip  the q1 logits path: k_q1_stats (+ _rl, _wide), k_q1_decode,

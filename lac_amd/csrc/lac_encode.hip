@@ -12,10 +12,13 @@
 //                 row scan + coder step + reset + flush + pack in one kernel.
 //   k_finish      flush (:193-202), carry resolution of bits() (:227-246), MSB-first
 //                 byte packing of group_bits (:336-347), one lane per stream.
+//   k_enc_drain   mid-job: each stream's settled prefix out as final bytes, the rest kept
+//                 (lac_encode_drain; rules in lac_drain.h), one wave per stream.
 //   k_pack        the multi-GPU gather's payload (lac_pack_jobs, lac_amd/dist.py).
 //   k_unpack      its inverse: packed jobs -> the aligned slots the decoders read
 //                 (lac_unpack_jobs, lac_decode_open_packed; rules in lac_wire.h).
 #include "lac_host.h"
+#include "lac_drain.h"
 #include "lac_wire.h"
 
 #include <type_traits>
@@ -656,6 +659,93 @@ __global__ void k_enc_rebase(EncState *states, int64_t B) {
     states[b] = st;
 }
 
+// k_enc_drain (lac_encode_drain): one wave per stream moves the stream's settled prefix, resolved
+// to big-endian bytes, behind the fill[b] bytes of the caller's slot b and keeps the other words
+// at the front of the planes (lac_drain.h has the two rules and every test; drain_stream_host
+// there is this kernel in plain loops).  Lane j of a block of 64 words holds word top - 1 - j, so
+// lane 0 is the block's least significant word.  Finding g: one ballot of the guard test per
+// block of words below the active one, from the high index down.  Resolving [0, g): per block
+// two ballots (generate, propagate) and one 64-bit add give every lane its carry-in
+// (drain::block_carries); the carry between blocks is a scalar.  Moving: ascending blocks, each
+// read whole before it is written; a block's destination lies below every later block's source
+// (g >= 1), so one wave in program order is safe.  Loads are clamped, never predicated
+// (load_vec_or0's reason).  Words 0..wlast are read and nothing beyond: the cost follows the bits
+// a stream holds, not cap_words.  All values that steer a loop are wave-uniform.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_enc_drain(EncState *states, uint64_t *planeA,
+                                                                   uint64_t *planeC, uint64_t cap_words, int64_t B,
+                                                                   int prec, uint8_t *dst, uint64_t dst_stride,
+                                                                   uint64_t *fill) {
+    const int lane = (int)lane_id();
+    const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + wave_in_block();
+    if (b >= B) return;
+    const EncState st = states[b];
+    if (drain::is_idle(__builtin_amdgcn_readfirstlane(st.err), __builtin_amdgcn_readfirstlane(st.nflush),
+                       rfl_u64(st.L)))
+        return;
+    const uint64_t L = rfl_u64(st.L), wlast = (L - 1) >> 6;
+    if (wlast >= cap_words) return;                           // (no state the encoders or set_state leave)
+    const uint64_t wa = rfl_u64(st.wa), wc = rfl_u64(st.wc);
+    uint64_t *pa = planeA + (uint64_t)b * cap_words, *pc = planeC + (uint64_t)b * cap_words;
+    // g, the low word sg and the carry-out cy of word g
+    uint64_t g = 0, sg = 0, cy = 0;
+    const bool certain = drain::is_certain((int64_t)rfl_u64((uint64_t)st.l), (int64_t)rfl_u64((uint64_t)st.h), prec);
+    if (certain) {
+        g = wlast;
+        sg = drain::resolve_word(wa, wc, 0, &cy);
+    } else {
+        for (uint64_t top = wlast; top > 0; top = top > 64 ? top - 64 : 0) {
+            const bool in = (uint64_t)lane < top;
+            const uint64_t i = in ? top - 1 - (uint64_t)lane : 0;
+            const uint64_t a = pa[i], c = pc[i];
+            uint64_t co;
+            const uint64_t s = drain::resolve_word(a, c, 0, &co);
+            const uint64_t m = __ballot(in && drain::is_guard(a, c));
+            if (m) {
+                const int first = __builtin_ctzll(m);         // the lowest lane: the highest index
+                g = top - 1 - (uint64_t)first;
+                sg = rfl_u64(shfl_u64(s, first));
+                cy = (__ballot(co != 0) >> first) & 1;
+                break;
+            }
+        }
+    }
+    if (g == 0) return;
+    const uint64_t f = rfl_u64(fill[b]);
+    if (!drain::slot_fits(g, f, dst_stride)) return;          // all or nothing: a later call with room takes it
+    // words [0, g) resolved backward from cy, out as big-endian words
+    uint64_t *out = reinterpret_cast<uint64_t *>(dst + (uint64_t)b * dst_stride + f);
+    uint64_t carry = cy;
+    for (uint64_t top = g; top > 0; top = top > 64 ? top - 64 : 0) {
+        const bool in = (uint64_t)lane < top;
+        const uint64_t i = in ? top - 1 - (uint64_t)lane : 0;
+        const uint64_t a0 = pa[i], c0 = pc[i];
+        const uint64_t a = in ? a0 : 0, c = in ? c0 : 0;
+        uint64_t co;
+        const uint64_t s = drain::resolve_word(a, c, 0, &co);
+        const uint64_t gen = __ballot(co != 0), prop = __ballot(s == ~0ull);
+        uint64_t cout;
+        const uint64_t cin = drain::block_carries(gen, prop, carry, &cout);
+        if (in) out[i] = drain::to_big_endian(s + ((cin >> lane) & 1));
+        carry = cout;
+    }
+    // words g..wlast to the front; word g resolved, the active word from the state
+    const uint64_t nk = wlast - g + 1;
+    for (uint64_t base = 0; base < nk; base += 64) {
+        const uint64_t j = base + (uint64_t)lane;
+        const bool in = j < nk;
+        const uint64_t src = g + (in ? j : 0);
+        uint64_t a = pa[src], c = pc[src];
+        if (j == 0) { a = sg; c = 0; }
+        if (j == nk - 1) { a = certain ? sg : wa; c = certain ? 0 : wc; }
+        if (in) { pa[j] = a; pc[j] = c; }
+    }
+    if (lane == 0) {
+        states[b].L = L - 64 * g;
+        if (certain) { states[b].wa = sg; states[b].wc = 0; }
+        fill[b] = f + 8 * g;
+    }
+}
+
 __global__ void k_enc_reset(EncState *states, int64_t B, int prec) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -798,6 +888,21 @@ int lac_encode_rebase(lac_ctx *c, void *stream) {
     if (c->mode != 0) return fail(LAC_E_STATE, "context is decoding");
     HIPCHK(hipSetDevice(c->device));
     k_enc_rebase<<<(unsigned)((c->B + 255) / 256), 256, 0, S(stream)>>>(c->enc, c->B);
+    CHECK_LAUNCH();
+    return LAC_OK;
+}
+
+int lac_encode_drain(lac_ctx *c, uint8_t *dst_dev, uint64_t dst_stride_bytes, uint64_t *fill_dev, void *stream) {
+    if (!c) return fail(LAC_E_ARG, "ctx is NULL");
+    if (c->mode != 0) return fail(LAC_E_STATE, "context is decoding");
+    if (c->finished)
+        return fail(LAC_E_STATE, "the streams are finished (plane A holds their packed bytes): lac_encode_reset first");
+    if (!dst_dev || !fill_dev) return fail(LAC_E_ARG, "dst_dev and fill_dev must not be NULL");
+    if ((uintptr_t)dst_dev % 8 || (uintptr_t)fill_dev % 8 || dst_stride_bytes % 8)
+        return fail(LAC_E_ARG, "dst_dev, fill_dev and dst_stride_bytes must be multiples of 8");
+    HIPCHK(hipSetDevice(c->device));
+    k_enc_drain<<<(unsigned)((c->B + kWavesPerBlock - 1) / kWavesPerBlock), 64 * kWavesPerBlock, 0, S(stream)>>>(
+        c->enc, c->planeA, c->planeC, c->cap_words, c->B, c->prec, dst_dev, dst_stride_bytes, fill_dev);
     CHECK_LAUNCH();
     return LAC_OK;
 }

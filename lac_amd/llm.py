@@ -241,9 +241,20 @@ class LogitsCompressor:
       [B, T] forward (not-yet-decoded positions 0) before each step -- under the
       causal mask position t never depends on later ones, and equal shapes select
       the same kernels.  O(T) full forwards: for modules without a cache.
+
+    ``drain_every=N`` (incremental compress only): the coder is sized for N positions, not
+    for T -- ``N * (prec + 2) + 256`` bits plus ``DRAIN_KEEP_BITS`` for the words a drain
+    holds back -- and its settled output is drained to the host every N positions
+    (``lac_amd.batch.DrainSink``, include/lac.h lac_encode_drain), so the device memory of a
+    session no longer grows with its length.  The output is identical.  The teacher-forced
+    ``encode_logits_job`` path is one launch and does not drain: it is sized for T as before.
     """
 
-    def __init__(self, module, vocab, prec=48, bos=1, logits_dtype=None, device="cuda", q1_step="auto"):
+    DRAIN_KEEP_BITS = 32 * 64   # room for the kept words: a drain keeps <= 8 on the streams measured (a run of
+                                # 0s or 1s, tests/test_drain_host.py); a stream that keeps more ends in LAC_E_CAPACITY
+
+    def __init__(self, module, vocab, prec=48, bos=1, logits_dtype=None, device="cuda", q1_step="auto",
+                 drain_every=None):
         import torch
         from .batch import logits_row_multiple
         self.module = module.to(device).eval()
@@ -251,6 +262,9 @@ class LogitsCompressor:
         self.dtype = logits_dtype or torch.bfloat16
         self.device = torch.device(device)
         self.q1_step = q1_step            # BatchCoder.set_q1_step: how the per-position calls run
+        if drain_every is not None and int(drain_every) < 1:
+            raise ValueError("drain_every: a number of positions >= 1, or None")
+        self.drain_every = None if drain_every is None else int(drain_every)
         self.incremental = hasattr(module, "step") and hasattr(module, "init_cache")
         # the logits kernels read rows as 16-B vectors: a vocab that is not a multiple
         # of 8 (bf16) / 4 (f32) -- GPT-2's 50257, say -- is coded over rows padded
@@ -291,10 +305,10 @@ class LogitsCompressor:
             return self._logits(ctx)
         return torch.cat([lg for _, lg in self._steps(B, T, lambda t: tokens[:, t])], 0).transpose(0, 1)
 
-    def _coder(self, B, T):
+    def _coder(self, B, T, keep_bits=0):
         from .batch import BatchCoder
-        coder = BatchCoder(self.vcode, B, prec=self.prec, pmf_bits=32, capacity_bits=T * (self.prec + 2) + 256,
-                           device=self.device)
+        coder = BatchCoder(self.vcode, B, prec=self.prec, pmf_bits=32,
+                           capacity_bits=T * (self.prec + 2) + 256 + keep_bits, device=self.device)
         coder.set_q1_step(self.q1_step)
         return coder
 
@@ -312,7 +326,8 @@ class LogitsCompressor:
         import torch
         tokens = tokens.to(self.device, torch.long)
         B, T = tokens.shape
-        coder = self._coder(B, T)
+        N = self.drain_every if self.incremental else None
+        coder = self._coder(B, T) if N is None else self._coder(B, min(N, T), self.DRAIN_KEEP_BITS)
         if lengths is not None:
             n = self._lengths(lengths, B, T)
             coder.set_stream_lengths(n)
@@ -322,8 +337,18 @@ class LogitsCompressor:
         if self.incremental:
             sym = tokens.t().contiguous().to(torch.int32)          # [T, B]
             coder.reset()
+            sink = None
+            if N is not None:
+                from .batch import DrainSink
+                sink = DrainSink(coder)
             for t, lg in self._steps(B, T, lambda t: tokens[:, t]):
                 coder.encode_logits_step(lg, sym[t:t + 1])
+                if sink is not None and (t + 1) % N == 0:
+                    sink.pull()
+            if sink is not None:
+                out = sink.finish()
+                coder.close()
+                return out
             coder.finish()
         else:
             coder.encode_logits_job(self.logits(tokens).transpose(0, 1), tokens.t().contiguous().to(torch.int32))
