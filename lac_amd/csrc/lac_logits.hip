@@ -771,6 +771,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
     constexpr int N = LogitN<LT>::N, R = 8, L = 8, NW = 16, NRB = 1024 / NT, NWR = NT / 64;
     constexpr int SL = (L - 1) * NT + LASTN;                   // slot vectors per row
     constexpr bool IMAX = LAC_Q1_IMAX && sizeof(LT) == 2;
+    static_assert(R == kRLRegVec && L == kRLSlots, "q1_slot_cap (lac_select.h) counts these vectors");
     static_assert((R + L) * N <= 128, "lane sums must fit 32 bits");
     // (not the bf16 8-copy decode forms, which sit at the 128-VGPR cap: two more live
     // registers there add spills)
@@ -1163,7 +1164,7 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
                                                           int64_t G, RowStats *__restrict__ out,
                                                           uint64_t *__restrict__ chunks, float *__restrict__ mrow,
                                                           uint64_t *__restrict__ xch, int split, int kg, int rpx) {
-    constexpr int N = LogitN<LT>::N, NT = 512, NW = 8;
+    constexpr int N = LogitN<LT>::N, NT = kQ1WideThreads, NW = NT / 64;
     constexpr bool IMAX = LAC_Q1_IMAX && sizeof(LT) == 2;
     static_assert(R % 8 == 0, "group totals in batches of 8 vectors");
     __shared__ uint32_t tabr[LAC_Q1_TAB_SIZE * kQ1Rep];

@@ -18,13 +18,15 @@
 // k_q1_stats_rl: 8 table copies beside all 8 LDS slots, or 16 where the row needs only
 // kRLLastTrim threads' worth of the last slot
 constexpr int kRLRep = 8;
+constexpr int kRLRegVec = 8, kRLSlots = 8;       // 16-B vectors per thread in registers, then in LDS slots
 constexpr int kRLLastTrim = 704;                 // last-slot threads of the 16-copy form
 constexpr int kRLTrimMaxVec = 15 * 1024 + kRLLastTrim;   // rows it holds: 16064 vectors
 // k_q1_stats_wide: vectors per thread of a 512-thread block
 constexpr int kQ1WideR = 40;
-constexpr int kQ1WideMaxVec = 512 * kQ1WideR;                  // registers only
+constexpr int kQ1WideThreads = 512;
+constexpr int kQ1WideMaxVec = kQ1WideThreads * kQ1WideR;       // registers only
 constexpr int kQ1WideL = 11;                                   // + LDS slots (the 32-copy table beside them)
-constexpr int kQ1WideSlotMaxVec = 512 * (kQ1WideR + kQ1WideL);
+constexpr int kQ1WideSlotMaxVec = kQ1WideThreads * (kQ1WideR + kQ1WideL);
 constexpr int kQ1MaxSeg = 16;                    // segments per row (lanes polling partners)
 
 // Row-group shapes (waves per row RW, 16-B vectors per thread R, rolling
@@ -70,7 +72,9 @@ inline int q1_rl_lastn(int nrb, bool rep16) {                     // threads' wo
     return !rep16 ? nt : nrb == 1 ? kRLLastTrim : nrb == 2 ? 320 : 192;
 }
 // vectors a row slot holds: 8 in registers + 7 full LDS slots per thread, and the last slot
-inline int64_t q1_slot_cap(int nrb, bool rep16) { return 15 * (1024 / nrb) + q1_rl_lastn(nrb, rep16); }
+inline int64_t q1_slot_cap(int nrb, bool rep16) {
+    return (int64_t)(kRLRegVec + kRLSlots - 1) * (1024 / nrb) + q1_rl_lastn(nrb, rep16);
+}
 // the fewest segments, kmin (at least 2) .. kmax, of whole 64-vector groups, each within lim vectors
 inline bool q1_split(int64_t nvec, int64_t kmin, int64_t kmax, int64_t lim, Q1Group *g) {
     const int64_t ngrp = (nvec + 63) / 64;

@@ -44,6 +44,24 @@ void sc_consts(int64_t *o) {
     for (int i = 0; i < 12; i++) o[i] = v[i];
 }
 
+// Where the kernels' position-dependent arithmetic changes (tests/positions.py).
+// o[6]: kRLRegVec, kRLSlots, kQ1WideThreads, kQ1WideMaxVec, kQ1WideSlotMaxVec, kQ1StepMaxVec
+void sc_layout_consts(int64_t *o) {
+    const int64_t v[6] = {kRLRegVec, kRLSlots, kQ1WideThreads, kQ1WideMaxVec, kQ1WideSlotMaxVec, kQ1StepMaxVec};
+    for (int i = 0; i < 6; i++) o[i] = v[i];
+}
+
+// o[4]: fused, rc, threads, R of the one-position step
+void sc_q1_step_plan(int cus, int64_t V, int type_bytes, int64_t streams, int mode, int64_t *o) {
+    const Q1StepPlan p = q1_step_plan(cus, V, type_bytes, streams, mode);
+    o[0] = p.fused, o[1] = p.rc, o[2] = p.threads, o[3] = p.R;
+}
+
+// k_decode_lean's chunks of a row of pmf_bits entries, vec per 16-byte load; o[2]: iterations per chunk, chunks
+void sc_lean_chunks(int64_t V, int vec, int pmf_bits, int64_t *o) {
+    lean_chunk_layout_n(V, vec, pmf_bits == 64 ? LeanCW<uint64_t> : LeanCW<uint32_t>, &o[0], &o[1]);
+}
+
 // kn[10]: dpath, wave_decode_min_streams, block_decode_min_streams, block_window_lo, block_window_hi,
 // block_waves, fine_decode, dec_stop, has_len, chunk_steps
 // o[12]: rc, path, vec, fine_nr, block_nw, G, step_waves, lean, CI, cs, help, static_rows

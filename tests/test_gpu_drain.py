@@ -421,3 +421,278 @@ def test_logits_compressor_with_drains():
     assert got == want and (np.asarray(gbits) == np.asarray(wbits)).all()
     assert int(np.asarray(wbits).min()) > 64                    # more than a word each: the drains had work
     assert torch.equal(lc.decompress(got, gbits, T).cpu(), tokens)
+
+
+# ------------------------------------------------------------------ 10. more than one block of 64 words
+# k_enc_drain works in blocks of 64 plane words (guard search, block_carries with a scalar carry
+# between blocks, the move loop); the cases above hold a few words per stream.  Here the planes
+# hold 60..200 words, planted with restore(); the reference is Python integers.
+WORDS = 208                                                     # the planted coder's capacity
+PREC_P = 48
+OPEN_P = ((1 << PREC_P) - 10, (1 << PREC_P) - 10 + (1 << (PREC_P - 1)) + 5)   # h >= 2^prec: not certain
+CERTAIN_P = (5, (1 << (PREC_P - 1)) + 100)
+
+
+def _top_bits(L, pattern=ONES):
+    """An active word: `pattern` cut to the bits the word holds when the stream is L bits long."""
+    used = ((L - 1) & 63) + 1
+    return (pattern >> (64 - used)) << (64 - used) & ONES
+
+
+def _last_bit(L):
+    return 1 << (63 - ((L - 1) & 63))
+
+
+def _reference(regs, L, A, C, prec=PREC_P):
+    """R = A + C + flush * 2^pad in Python integers -> (bytes, bit count), finish_stream's result."""
+    digits = _flush_digits(*regs, prec)
+    F = 0
+    for d in digits:
+        F = 2 * F + d
+    Lf = L + len(digits)
+    nwords = (Lf + 63) // 64
+    val = lambda ws: sum(int(w) << (64 * (nwords - 1 - i)) for i, w in enumerate(ws))   # noqa: E731
+    R = val(A) + val(C) + (F << (nwords * 64 - Lf))
+    assert 0 <= R < 1 << (64 * nwords) and len(A) == len(C) == ((L - 1) >> 6) + 1 <= nwords
+    return R.to_bytes(8 * nwords, "big")[:(Lf + 7) // 8], Lf
+
+
+def _settled(regs, L, A, C, prec=PREC_P):
+    """The two rules of lac_drain.h restated: the words a drain emits."""
+    wlast = (L - 1) >> 6
+    if L <= 64:
+        return 0
+    if regs[0] >= 0 and regs[1] < 1 << prec:
+        return wlast
+    for i in range(wlast - 1, -1, -1):
+        if (int(A[i]) + int(C[i])) & ONES not in (0, ONES):
+            return i
+    return 0
+
+
+def _planted(cases, words):
+    """cases: [(registers, L, A words 0..wlast, C words 0..wlast)] -> a checkpoint of a coder of `words`
+    words holding one per stream."""
+    from lac_amd.batch import ENC_STATE
+    st = np.zeros(len(cases), dtype=ENC_STATE)
+    planes = np.zeros((2, len(cases), words), dtype=np.uint64)
+    for b, ((l, h), L, A, C) in enumerate(cases):
+        st[b] = (l, h, L, A[-1], C[-1], 7, 0, -1, -1, [0] * 8)
+        planes[0, b, :len(A)], planes[1, b, :len(C)] = A, C
+    return {"state": st, "planes": planes, "prec": PREC_P, "vocab": 16}
+
+
+def _planted_coder(n):
+    from lac_amd.batch import BatchCoder
+    c = BatchCoder(16, n, prec=PREC_P, capacity_bits=WORDS * 64, device=DEV)
+    assert c.bits_stride() // 8 >= WORDS
+    return c
+
+
+def _drain_planted(cases):
+    """Plant, finish with no drain; plant again, drain once, finish: both are the reference's bytes,
+    and the drain emitted the words the rules name.  -> g per stream."""
+    from lac_amd.batch import DrainSink
+    want = [_reference(*case) for case in cases]
+    gs = [_settled(*case) for case in cases]
+    with _planted_coder(len(cases)) as c:
+        ck = _planted(cases, c.bits_stride() // 8)
+        c.restore(ck)
+        c.finish()
+        plain, pbits = c.to_bytes()
+        assert [int(v) for v in pbits] == [w[1] for w in want] and plain == [w[0] for w in want]
+        c.reset()
+        c.restore(ck)
+        sink = DrainSink(c)
+        n = sink.pull()
+        assert n.tolist() == [8 * g for g in gs]
+        assert c.checkpoint()["state"]["L"].tolist() == [case[1] - 64 * g for case, g in zip(cases, gs)]
+        for b, (g, (data, _)) in enumerate(zip(gs, want)):      # the drained words are already final
+            assert bytes(sink.parts[b]) == data[:8 * g], b
+        got, gbits = sink.finish()
+        assert [int(v) for v in gbits] == [w[1] for w in want]
+        bad = [b for b in range(len(cases)) if got[b] != want[b][0]]
+        assert not bad, bad
+    return gs
+
+
+def _random_words(rng, n):
+    return [int(v) for v in rng.integers(0, 1 << 63, size=n, dtype=np.uint64) * 2 + rng.integers(0, 2, size=n,
+                                                                                                  dtype=np.uint64)]
+
+
+def test_drain_guard_far_below_the_active_word():
+    """Open registers, L = 150 * 64 + 20: words 4..149 all ones, the guard at word 3, a pending C
+    bit on the active word.  The guard search crosses two whole blocks without a hit, the move
+    loop moves three blocks of kept words, and the finish ripples the carry through them."""
+    L = 150 * 64 + 20
+    A = [5, 0x77, 9, 0x1234] + [ONES] * 146 + [_top_bits(L)]
+    C = [0] * 150 + [_last_bit(L)]
+    assert _drain_planted([(OPEN_P, L, A, C)]) == [3]
+
+
+def test_drain_certain_carry_through_149_words():
+    """Certain registers: word 148 generates (A all ones, C = 1: its low word is 0, no guard), words
+    1..147 are all ones, word 0 = 5.  g = wlast = 149: three blocks resolved, the scalar carry
+    crossing both block edges into word 0."""
+    L = 149 * 64 + 20
+    A = [5] + [ONES] * 148 + [_top_bits(L, 0xABCDE << 44)]
+    C = [0] * 148 + [1, 0]
+    assert _drain_planted([(CERTAIN_P, L, A, C), (OPEN_P, L, A, C)]) == [149, 0]
+    want, _ = _reference(CERTAIN_P, L, A, C)
+    assert want[:8] == (6).to_bytes(8, "big") and want[8:149 * 8] == bytes(148 * 8)
+
+
+def test_drain_chains_on_block_edges():
+    """With g words drained, block k of the resolve loop holds words g - 64 k - 1 (lane 0) down to
+    g - 64 k - 64 (lane 63).  A generate in the last lane of a block with the propagate run ending
+    in the first lane of the next; the mirror image (generate in a block's first lane, the run
+    ending in that block); runs that cover a whole block or two.  Each in both register kinds: open,
+    the guard is word g above the chain and g words drain; certain, g + 1 words drain, which moves
+    every chain one lane on, so each edge is met from both sides."""
+    cases = []
+    for g in (140, 129):
+        for gen, run, tail in ((g - 64, 1, 0), (g - 63, 1, 0), (g - 65, 1, 0), (g - 65, 63, 0), (g - 1, 64, 0),
+                               (g - 64, 64, 0), (g - 1, 127, 0), (g - 63, 1, 1)):
+            rng = np.random.default_rng(gen * 1000 + run)
+            L = (g + 1) * 64 + 9
+            A = [w | 2 for w in _random_words(rng, g)] + [0x42, _top_bits(L, 0x5A5A << 48)]   # (no chance all-ones)
+            C = [0] * (g + 2)
+            A[0] = 3
+            A[gen], C[gen] = ONES - 6, 7 + tail                 # wraps: generates, low word 0 or 1
+            for i in range(gen - run, gen):
+                A[i] = ONES                                     # the propagate run; the word below it absorbs
+            cases.append((CERTAIN_P, L, A, C))
+            # open: word g (0x42) is the guard, the same chain below it
+            cases.append((OPEN_P, L, A, C))
+    gs = _drain_planted(cases)
+    assert gs[::2] == [141] * 8 + [130] * 8                     # certain: all but the active word
+    assert gs[1::2] == [140] * 8 + [129] * 8                    # open: up to the guard
+
+
+@pytest.mark.parametrize("g", [63, 64, 65, 128, 129])
+def test_drain_exactly_g_words(g):
+    """g on either side of one and two blocks: by rule 2 (certain, g = wlast) and by rule 1 (the
+    guard at word g under all-ones / all-zero words up to the active one)."""
+    rng = np.random.default_rng(g)
+    L = g * 64 + 33
+    A = _random_words(rng, g) + [_top_bits(L, 0x123456789 << 28)]
+    A[0] = 1
+    certain = (CERTAIN_P, L, A, [0] * (g + 1))
+    cases = [certain]
+    for above, fillw in ((1, ONES), (3, 0), (64, ONES), (65, ONES), (70, 0)):
+        wl = g + above                                          # the guard is `above` words below the active word
+        L2 = wl * 64 + 20
+        A2 = _random_words(rng, g) + [0x1234] + [fillw] * (above - 1) + [_top_bits(L2)]
+        A2[0] = 1
+        C2 = [0] * wl + [_last_bit(L2)]
+        cases.append((OPEN_P, L2, A2, C2))
+    assert _drain_planted(cases) == [g] * 6
+
+
+def test_drain_guard_in_the_last_lane_of_block_one_and_the_first_of_block_two():
+    """The guard search's lane j of its first block is word wlast - 1 - j: a guard 64 words below the
+    active word sits in the block's last lane, one 65 below in the next block's first; everything
+    above it is all ones.  wlast = 64 / 65 / 66 put those guards at words 0, 1 and 2."""
+    cases = []
+    for wl in (100, 64, 65, 66, 129):
+        for below in (64, 65):
+            if wl - below < 0:
+                continue
+            L = wl * 64 + 1
+            A = [ONES] * wl + [_top_bits(L)]
+            A[0] = 2
+            A[wl - below] = 0x99 if wl - below else 2
+            cases.append((OPEN_P, L, A, [0] * wl + [_last_bit(L)]))
+    gs = _drain_planted(cases)
+    assert gs == [36, 35, 0, 1, 0, 2, 1, 65, 64]
+
+
+def test_drain_slot_fits_more_than_a_block_exactly_or_not_at_all():
+    """g = 100 words behind a non-zero fill: a slot with exactly 800 bytes of room takes them, one
+    with 792 takes nothing and the stream stays as it was; the bytes around the slots stay."""
+    rng = np.random.default_rng(100)
+    g, B = 100, 4
+    L = g * 64 + 40
+    cases = []
+    for b in range(B):
+        A = _random_words(rng, g) + [_top_bits(L, 0xF0F0F0F0F0 << 24)]
+        A[0] = 7
+        cases.append((CERTAIN_P, L, A, [1 if i % 5 == 0 else 0 for i in range(g)] + [0]))
+    want = [_reference(*case)[0] for case in cases]
+    with _planted_coder(B) as c:
+        ck = _planted(cases, c.bits_stride() // 8)
+        c.restore(ck)
+        stride = 8 * g + 48
+        buf = torch.full((16 + B * stride + 16,), SENTINEL, dtype=torch.uint8, device=DEV)
+        slots = buf[16:16 + B * stride].view(B, stride)
+        start = np.array([48, 56, 40, 48], dtype=np.int64)      # exact, one word short, a word to spare, exact
+        fill = torch.from_numpy(start.copy()).to(DEV)
+        c.drain(slots, fill)
+        got, f = buf.cpu().numpy(), fill.cpu().numpy()
+        body = got[16:16 + B * stride].reshape(B, stride)
+        assert (got[:16] == SENTINEL).all() and (got[16 + B * stride:] == SENTINEL).all()
+        assert f.tolist() == [stride, 56, 40 + 8 * g, stride]
+        now = c.checkpoint()
+        for b in range(B):
+            assert (body[b, :start[b]] == SENTINEL).all() and (body[b, f[b]:] == SENTINEL).all()
+            if b == 1:
+                assert (body[b] == SENTINEL).all() and _same_stream(now, ck, b)
+            else:
+                assert body[b, start[b]:f[b]].tobytes() == want[b][:8 * g], b
+                assert now["state"]["L"][b] == L - 64 * g
+        fill[1] = 48                                            # the next call, with room, takes it
+        c.drain(slots, fill)
+        assert int(fill[1]) == stride
+        assert buf.cpu().numpy()[16 + stride:16 + 2 * stride][48:].tobytes() == want[1][:8 * g]
+        c.finish()
+        tail, _ = c.to_bytes()
+        assert [want[b][:8 * g] + tail[b] for b in range(B)] == want
+
+
+def test_drain_random_planes_of_200_words():
+    """20 seeded streams of 200 words: random A, sparse C bits, planted runs of all-ones and
+    all-zero words (some right below the active word, some across block edges); both rules."""
+    rng = np.random.default_rng(2026)
+    cases = []
+    for s in range(20):
+        wl = 199 + int(rng.integers(0, 5))
+        L = wl * 64 + int(rng.integers(1, 65))
+        A = _random_words(rng, wl) + [_top_bits(L, int(rng.integers(0, 1 << 63)) * 2 + 1)]
+        C = [(1 << int(rng.integers(0, 64))) if rng.random() < 0.1 else 0 for _ in range(wl)] + [
+            _last_bit(L) if rng.random() < 0.5 else 0]
+        for _ in range(int(rng.integers(1, 5))):                # runs of propagating / empty words
+            a = int(rng.integers(1, wl))
+            n = int(rng.integers(1, 90))
+            fillw = ONES if rng.random() < 0.7 else 0
+            for i in range(a, min(a + n, wl)):
+                A[i], C[i] = fillw, 0
+            if rng.random() < 0.5 and a + n < wl:               # a generate feeding the run
+                A[min(a + n, wl - 1)], C[min(a + n, wl - 1)] = ONES, 1 << int(rng.integers(0, 8))
+        if s % 4 < 2:                                           # nothing but a run up to the active word
+            top = int(rng.integers(1, 140))
+            for i in range(wl - top, wl):
+                A[i], C[i] = ONES, 0
+        A[0], C[0] = int(rng.integers(1, 1 << 32)), 0           # room for the last carry
+        cases.append((OPEN_P if s % 2 else CERTAIN_P, L, A, C))
+    gs = _drain_planted(cases)
+    assert len({g // 64 for g in gs}) >= 3 and min(gs[1::2]) < 128 < max(gs), gs
+
+
+def test_bounded_coder_drains_a_hundred_words_at_a_time():
+    """The u64 tables of _int_case (~22 bits per symbol) in a coder sized for 300 steps, drained every
+    300 steps: every drain moves more than one block of words per stream."""
+    from lac_amd.batch import BatchCoder, DrainSink
+    dp, ds, want, wbits = _int_case(64)
+    cap = 300 * (PREC1 + 2) + 256
+    with BatchCoder(V1, B1, prec=PREC1, pmf_bits=64, capacity_bits=cap, device=DEV) as c:
+        sink = DrainSink(c)
+        c.reset()
+        moved = []
+        for t in range(0, T1, 300):
+            c.encode(dp[t:t + 300], ds[t:t + 300])
+            moved.append(sink.pull())
+        got, gbits = sink.finish()
+        assert (gbits == wbits).all()
+        assert got == want
+        assert len(moved) == 2 and all(int(n.min()) > 64 * 8 for n in moved), [int(n.min()) for n in moved]

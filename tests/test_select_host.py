@@ -6,15 +6,10 @@ no GPU needed.  The expectations are DESIGN.md sections 1 / 5 / 5b and the comme
 each rule, restated here by hand: a rule change shows up as a failing line to re-decide.
 """
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import REPO
-
-SO = os.path.join(REPO, "tests", "native", "libselectcheck.so")
-SRC = os.path.join(REPO, "tests", "native", "select_check.cpp")
+import positions
 
 LAC_OK, LAC_E_ARG = 0, -1
 TILED, RL, WIDE, RL_GROUP, WIDE_GROUP = range(5)
@@ -39,21 +34,7 @@ class Plan(dict):
 
 @pytest.fixture(scope="module")
 def sel():
-    hdr = os.path.join(REPO, "lac_amd", "csrc", "lac_select.h")
-    deps = [SRC, hdr, os.path.join(REPO, "include", "lac.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.run(["hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(REPO, "lac_amd", "csrc"),
-                        "-I", os.path.join(REPO, "include"), SRC, "-o", SO], check=True)
-    lib = C.CDLL(SO)
-    i64p = C.POINTER(C.c_int64)
-    lib.sc_q1_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, i64p]
-    lib.sc_q1_group.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, i64p]
-    lib.sc_q1_slot_cap.restype = C.c_int64
-    lib.sc_q1_slot_cap.argtypes = [C.c_int, C.c_int]
-    lib.sc_consts.argtypes = [i64p]
-    lib.sc_decode_plan.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
-                                   C.c_int64, i64p]
-    lib.sc_decode_plan.restype = None
+    lib = positions.load_select()                             # compiled when stale, every sc_* declared there
     buf = (C.c_int64 * 12)()
     lib.sc_consts(buf)
     lib.K = Plan(zip(CONSTS, buf))
