@@ -432,6 +432,47 @@ int lac_decode_open_packed(lac_ctx *ctx, const uint8_t *src_dev, uint64_t src_by
                            const uint64_t *counts_dev, const uint64_t *base_dev, uint64_t *end_dev,
                            void *stream);
 
+/* Windowed decode, the mirror of lac_encode_drain: decode streams of any length through a
+ * window of W = ceil(capacity_bits / 64) + 1 words per stream that the context owns, so that
+ * capacity_bits bounds the bits decoded between two refills and not the stream.
+ *   lac_decode_open_window takes lac_decode_open's source (bits_dev, stride_bytes, nbits_dev:
+ * the same alignment rules; bits_dev == NULL is LAC_E_ARG) and borrows it until the next open or
+ * lac_close.  Only k_dec_refill ever reads the source, so it may be device memory or
+ * lac_host_alloc memory passed by its device address: the compressed data can stay on the host.
+ * The window -- [streams][8 W] bytes, streams counts and streams bases, allocated on first use,
+ * freed by lac_close, shared with lac_decode_open_packed's slots -- is filled from source word
+ * base_words_dev[b] on (uint64 [streams], device memory; NULL: 0 for every stream) and the
+ * decoder is opened on it: every decode path (split, fused, stats, block, lean), the logits
+ * decode and its one-position step, the tail, lac_decode_determined, lac_set_stream_lengths,
+ * LAC_OPT_DECODE_STOP and lac_decode_get_state / set_state read the window as they read any
+ * opened buffer.  A stream with nbits_dev[b] > 8 * stride_bytes or 64 * base > nbits_dev[b]
+ * fails with the sticky LAC_E_ARG and nothing of it is read.
+ *   lac_decode_refill slides every stream's window: the whole words below bit pos - prec are
+ * dropped (g = (pos - prec) >> 6), the kept words move to the front, g words come from the
+ * source, and pos shrinks by 64 g, base grows by g.  One launch (k_dec_refill, one wave per
+ * stream), asynchronous on `stream`, no host synchronisation, no allocation.  A window that
+ * reaches its stream's end stays where it is, as does a stream with a sticky error or one
+ * stopped at its count.  LAC_E_STATE unless the open decode is a windowed one.
+ *   lac_decode_window_base copies every stream's base to the host (synchronises).
+ * Contract, per stream: symbols, -1 fills, status and err_step, nsym, l / h / x, det / ndet and
+ * pos + 64 * base are those of lac_decode_open on the whole stream followed by the same decode
+ * calls (lac_amd/csrc/lac_refill.h: a decoder never reads below pos - prec, a step pulls at most
+ * prec bits, and everything derived from the stream's end uses pos - nbits only).
+ * lac_dec_state.pos is relative to the window; per-stream counts and LAC_OPT_DECODE_STOP mean
+ * what they did.  Resume: lac_decode_open_window with the saved bases, then
+ * lac_decode_set_state with the saved registers.
+ *   Sizing: after a refill pos <= prec + 63 and N steps add at most N * prec, so N steps between
+ * two refills are safe when 64 W >= (N + 1) * prec + 63; the encode side's
+ * capacity_bits = N * (prec + 2) + 256 satisfies it for every prec.
+ *   A stream whose steps read past the bits its window held while more of the stream lay outside
+ * it (a dry stream) is detected by the next refill, not by the steps: it gets the sticky
+ * LAC_E_CAPACITY with err_step = its nsym, and its symbols since the previous refill are void.
+ * Refill once after the last step before trusting lac_stream_status. */
+int lac_decode_open_window(lac_ctx *ctx, const uint8_t *bits_dev, uint64_t stride_bytes,
+                           const uint64_t *nbits_dev, const uint64_t *base_words_dev, void *stream);
+int lac_decode_refill(lac_ctx *ctx, void *stream);
+int lac_decode_window_base(lac_ctx *ctx, uint64_t *base_words_host, void *stream);
+
 /* Decode one symbol per stream from row b at pmf_dev + b*stream_stride. */
 int lac_decode_step(lac_ctx *ctx, const void *pmf_dev, int64_t stream_stride,
                     int32_t *sym_out_dev, void *stream);

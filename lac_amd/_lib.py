@@ -70,6 +70,9 @@ PROTOTYPES = [
     ("lac_flush_digits", _i, [_vp, _vp, _vp, _vp]),
     ("lac_encoder_registers", _i, [_vp, _vp, _vp, _vp]),
     ("lac_decode_open", _i, [_vp, _vp, _u64, _vp, _vp]),
+    ("lac_decode_open_window", _i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    ("lac_decode_refill", _i, [_vp, _vp]),
+    ("lac_decode_window_base", _i, [_vp, _vp, _vp]),
     ("lac_decode_step", _i, [_vp, _vp, _i64, _vp, _vp]),
     ("lac_decode_steps", _i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     ("lac_decode_determined", _i, [_vp, _vp, _vp]),

@@ -16,6 +16,7 @@ cross into liblac.so as raw device pointers (see include/lac.h).
 from __future__ import annotations
 
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -489,6 +490,61 @@ class BatchCoder:
                                               None if end is None else C.c_void_p(end.data_ptr()), self._stream))
         self._dec_keep = None                                 # the decoder reads the coder's own slots
 
+    def decode_open_window(self, bits, nbits=None, base=None):
+        """decode_open through a sliding window (include/lac.h lac_decode_open_window): the
+        coder keeps ``bits_stride()`` bytes per stream on the device and :meth:`refill` slides
+        them over streams of any length, so ``capacity_bits`` bounds the bits decoded between
+        two refills (``N * (prec + 2) + 256`` for N steps), not the stream.  ``bits``: a
+        :class:`HostBits` (the streams stay in host memory) or a uint8 device tensor
+        [streams, stride] with ``nbits`` as in :meth:`decode_open`; ``base``: None, or per
+        stream the source word the window starts at (a sequence or an 8-byte integer device
+        tensor [streams]) -- with :meth:`set_state`-style resume, what :meth:`window_base`
+        returned.  The source is borrowed until the next open.  Everything after it -- every
+        decode path, :meth:`set_stream_lengths`, :meth:`set_decode_stop`, the logits decode --
+        is what it is after :meth:`decode_open`; decoder positions are window-relative."""
+        torch = _torch()
+        if isinstance(bits, HostBits):
+            if bits.streams != self.streams or bits.device != self.device:
+                raise ValueError("HostBits of another stream count or device")
+            if bits.dev_addr is None:
+                raise ValueError("HostBits is closed")
+            ptr, stride, nbits = bits.dev_addr, bits.stride, bits.nbits
+        else:
+            if bits.dtype != torch.uint8 or bits.device != self.device:
+                raise TypeError("bits must be a uint8 tensor on the coder's device")
+            if bits.dim() != 2 or bits.shape[0] != self.streams or bits.stride(1) != 1:
+                raise ValueError("bits must be [streams, stride] with contiguous rows")
+            ptr, stride = bits.data_ptr(), bits.stride(0)       # (alignment: the library's LAC_E_ARG)
+        if nbits is None or nbits.dtype not in (torch.int64, torch.uint64) or nbits.device != self.device:
+            raise TypeError("nbits must be an int64/uint64 tensor on the coder's device")
+        if tuple(nbits.shape) != (self.streams,) or not nbits.is_contiguous():
+            raise ValueError(f"nbits must be a contiguous [{self.streams}] tensor")
+        if base is not None and not isinstance(base, torch.Tensor):
+            b = np.asarray(base)
+            if b.shape != (self.streams,) or b.dtype.kind not in "iu" or (b.size and int(b.min()) < 0):
+                raise ValueError(f"base must be {self.streams} integers >= 0")
+            base = torch.from_numpy(np.ascontiguousarray(b).astype(np.int64)).to(self.device)
+        if base is not None and (base.element_size() != 8 or base.is_floating_point() or base.device != self.device
+                                 or tuple(base.shape) != (self.streams,) or not base.is_contiguous()):
+            raise ValueError(f"base must be a contiguous 8-byte integer [{self.streams}] tensor on the coder's device")
+        check(self.lib.lac_decode_open_window(self.ctx, C.c_void_p(ptr), stride, C.c_void_p(nbits.data_ptr()),
+                                              None if base is None else C.c_void_p(base.data_ptr()), self._stream))
+        self._dec_keep = (bits, nbits, base)                  # borrowed by the library
+
+    def refill(self):
+        """Slide every stream's window up to the decoder's position (include/lac.h
+        lac_decode_refill): call it at least every N steps for a window sized for N, and once
+        after the last step -- a stream that outran its window is found here (sticky
+        LAC_E_CAPACITY in :meth:`status`), not by the steps.  One launch; no host sync."""
+        check(self.lib.lac_decode_refill(self.ctx, self._stream))
+
+    def window_base(self):
+        """Per stream: the source word the window starts at (uint64 [streams]); a decoder
+        position ``pos`` is bit ``pos + 64 * window_base()`` of the stream.  Synchronises."""
+        n = np.zeros(self.streams, dtype=np.uint64)
+        check(self.lib.lac_decode_window_base(self.ctx, n.ctypes.data_as(C.c_void_p), self._stream))
+        return n
+
     def determined(self):
         """Per stream: leading decoded symbols fixed by the available bits (the
         count the reference's A_from_bin.run(bits, stop=0) emits)."""
@@ -686,6 +742,64 @@ class DrainSink:
         tail, nb = self.coder.to_bytes()
         drained = np.array([len(p) for p in self.parts], dtype=np.uint64)
         return [bytes(p) + t for p, t in zip(self.parts, tail)], nb + 8 * drained
+
+
+class HostBits:
+    """Compressed streams kept in host memory for :meth:`BatchCoder.decode_open_window`, the
+    decode mirror of :class:`DrainSink`: the bytes stay on the host (liblac's lac_host_alloc,
+    pinned and mapped into the device, [streams, stride] with ``stride`` a multiple of 8) and
+    :meth:`BatchCoder.refill` reads only the words that enter a window, so the device holds
+    ``streams x window`` whatever the streams' length.  ``data``: per-stream ``bytes``;
+    ``nbits``: their bit counts (kept as a device tensor).
+
+        src = HostBits(data, nbits, coder.device)
+        coder.decode_open_window(src)
+        for t in range(T):
+            coder.decode(pmf[t:t + 1], out[t:t + 1])
+            if (t + 1) % 64 == 0:
+                coder.refill()
+        coder.refill()
+        src.close()                              # after the last refill has run
+    """
+
+    def __init__(self, data, nbits, device):
+        torch = _torch()
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.streams = len(data)
+        nb = np.ascontiguousarray(np.asarray(nbits).astype(np.int64))
+        if nb.shape != (self.streams,) or (nb.size and int(nb.min()) < 0):
+            raise ValueError(f"nbits must be {self.streams} counts >= 0")
+        for b, d in enumerate(data):
+            if 8 * len(d) < int(nb[b]):
+                raise ValueError(f"stream {b}: {len(d)} bytes hold fewer than {int(nb[b])} bits")
+        self.stride = max(8, (max((len(d) for d in data), default=0) + 7) // 8 * 8)
+        self.nbytes = self.stride * max(self.streams, 1)
+        h, d = C.c_void_p(), C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.lac_host_alloc(self.nbytes, C.byref(h), C.byref(d)))
+        self._h, self.dev_addr = h.value, d.value
+        self.array = np.ctypeslib.as_array((C.c_uint8 * self.nbytes).from_address(self._h)) \
+            .reshape(max(self.streams, 1), self.stride)
+        self.array[...] = 0
+        for b, s in enumerate(data):
+            self.array[b, :len(s)] = np.frombuffer(s, dtype=np.uint8)
+        self.nbits = torch.from_numpy(nb).to(self.device)
+
+    def close(self):
+        """Free the host memory: only once every refill that reads it has run."""
+        if getattr(self, "_h", None):
+            self.array = None
+            self.lib.lac_host_free(self._h)
+            self._h = self.dev_addr = None
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():                # (the HIP runtime may be torn down already)
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def logits_row_multiple(dtype) -> int:

@@ -97,6 +97,7 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->slen);
     (void)hipFree(c->ubits);
     (void)hipFree(c->unbits);
+    (void)hipFree(c->wbase);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;

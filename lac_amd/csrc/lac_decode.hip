@@ -5,11 +5,14 @@
 // renormalisation (emit_bit, :284-291).  At >= 2048 streams one launch per job with
 // one wave per stream (k_decode_wave_fine); fewer streams take the block and stats
 // paths (k_decode_block; k_dec_stats + k_decode_seq / k_decode_lean); the flush and
-// windows that leave [l, h] run in the reference's own frame (lac_tail.h).
+// windows that leave [l, h] run in the reference's own frame (lac_tail.h).  k_dec_refill
+// (lac_decode_open_window, lac_decode_refill; rules in lac_refill.h) keeps a window of the
+// context's capacity per stream and slides it, for streams of any length.
 #include <type_traits>
 
 #include "lac_host.h"
 #include "lac_dec_dev.h"
+#include "lac_refill.h"
 
 namespace {
 
@@ -1385,6 +1388,91 @@ __global__ __launch_bounds__(64) void k_decode_lean(const E *__restrict__ lcdf, 
     }
 }
 
+// k_dec_refill (lac_decode_open_window, lac_decode_refill): one wave per stream fills or slides
+// the stream's window of W words over its source (lac_refill.h has the rules, the sizing bound
+// and every test; open_stream_host / refill_stream_host there are this kernel in plain loops).
+// OPEN: the W words from source word base_in[b] on, the count and the base; DecState is not
+// touched (k_dec_init runs on the window next), and a bad source gets the count ~0, which
+// k_dec_init fails with the sticky LAC_E_ARG, and reads nothing.  Otherwise: a stream that ran
+// dry gets err / err_step and nothing else; a live one drops the g whole words below pos - prec,
+// moves the kept W - g words to the front -- ascending blocks of 64, each read whole before it is
+// written, the destination below every later source (g >= 1), so one wave in program order is
+// safe -- and takes g words from the source, which alone is read across the bus when the source
+// is host memory.  Loads are clamped, never predicated (load_vec_or0's reason): into [0, W) of
+// the window, into [0, nw) of the source, and a stream of no words loads nothing.  Stores stay in
+// [0, W) of the stream's slot.  All values that steer a loop are wave-uniform.
+template <bool OPEN>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_dec_refill(DecState *states, const uint8_t *__restrict__ src,
+                                                                   uint64_t src_stride,
+                                                                   const uint64_t *__restrict__ src_nbits,
+                                                                   const uint64_t *__restrict__ base_in, uint64_t *win,
+                                                                   uint64_t W, uint64_t *count, uint64_t *wbase,
+                                                                   int64_t B, int prec) {
+    const int lane = (int)lane_id();
+    const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + wave_in_block();
+    if (b >= B) return;
+    const uint64_t nb = rfl_u64(src_nbits[b]), nw = refill::stream_words(nb);
+    const uint64_t *sw = reinterpret_cast<const uint64_t *>(src + (uint64_t)b * src_stride);
+    uint64_t *mw = win + (uint64_t)b * W;
+    // window words [j0, W) from source word sbase + j: zero at or past word nw
+    auto fetch = [&](uint64_t j0, uint64_t sbase) {
+        for (uint64_t blk = j0; blk < W; blk += 64) {
+            const uint64_t j = blk + (uint64_t)lane;
+            const bool in = j < W;
+            const uint64_t i = sbase + (in ? j : blk);
+            uint64_t w = 0;
+            if (nw) {                                         // (uniform)
+                const uint64_t v = sw[i < nw ? i : nw - 1];
+                w = i < nw ? v : 0;
+            }
+            if (in) mw[j] = w;
+        }
+    };
+    if constexpr (OPEN) {
+        const uint64_t base = base_in ? rfl_u64(base_in[b]) : 0;
+        if (refill::bad_source(nb, base, src_stride)) {
+            if (lane == 0) {
+                count[b] = ~0ull;
+                wbase[b] = 0;
+            }
+            return;
+        }
+        fetch(0, base);
+        if (lane == 0) {
+            count[b] = refill::held_bits(nb, base, W);
+            wbase[b] = base;
+        }
+        return;
+    }
+    DecState st = states[b];
+    dec_state_uniform(st);
+    const uint64_t base = rfl_u64(wbase[b]), held = rfl_u64(count[b]);
+    if (st.err != 0 || refill::bad_source(nb, base, src_stride)) return;
+    const bool done = refill::complete(nb, base, W);
+    if (refill::ran_dry(st.pos, held, done)) {
+        if (lane == 0) {
+            states[b].err = LAC_E_CAPACITY;
+            states[b].err_step = st.nsym;
+        }
+        return;
+    }
+    if (done) return;
+    const uint64_t g = refill::drop_words(st.pos, prec);
+    if (g == 0 || g >= W) return;                             // (g < W: pos <= held <= 64 W)
+    const uint64_t nk = W - g;
+    for (uint64_t blk = 0; blk < nk; blk += 64) {
+        const uint64_t j = blk + (uint64_t)lane;
+        const bool in = j < nk;
+        const uint64_t w = mw[g + (in ? j : blk)];
+        if (in) mw[j] = w;
+    }
+    fetch(nk, base + g);
+    if (lane == 0) {
+        count[b] = refill::held_bits(nb, base + g, W);
+        wbase[b] = base + g;
+        states[b].pos = st.pos - 64 * g;
+    }
+}
 
 #include "lac_tail.h"
 
@@ -1609,6 +1697,7 @@ int lac_decode_open(lac_ctx *c, const uint8_t *bits_dev, uint64_t stride_bytes, 
     c->dstride = stride_bytes;
     c->dnbits = nbits_dev;
     c->mode = 1;
+    c->wsrc = nullptr;                                        // (lac_decode_open_window sets it after this open)
     k_dec_init<<<(unsigned)((c->B + 255) / 256), 256, 0, S(stream)>>>(c->dec, c->B, c->prec, bits_dev, stride_bytes,
                                                                       nbits_dev);
     CHECK_LAUNCH();
@@ -1631,6 +1720,53 @@ int lac_decode_open_packed(lac_ctx *c, const uint8_t *src_dev, uint64_t src_byte
     // a job that does not fit left every count at ~0, an over-long stream its claimed count:
     // k_dec_init fails those streams with the sticky LAC_E_ARG
     return lac_decode_open(c, c->ubits, stride, c->unbits, stream);
+}
+
+// The window is the unpacked slots' buffer (a context has one open decode at a time); the source
+// is read by k_dec_refill alone.
+int lac_decode_open_window(lac_ctx *c, const uint8_t *bits_dev, uint64_t stride_bytes, const uint64_t *nbits_dev,
+                           const uint64_t *base_words_dev, void *stream) {
+    if (!c) return fail(LAC_E_ARG, "ctx is NULL");
+    if (!bits_dev || !nbits_dev) return fail(LAC_E_ARG, "bits_dev and nbits_dev must not be NULL");
+    if (stride_bytes % 8 || (uintptr_t)bits_dev % 8) return fail(LAC_E_ARG, "bit buffers must be 8-byte aligned");
+    if ((uintptr_t)nbits_dev % 8 || (uintptr_t)base_words_dev % 8)
+        return fail(LAC_E_ARG, "nbits_dev and base_words_dev must be 8-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t stride = c->cap_words * 8;
+    if (!c->ubits) HIPCHK(hipMalloc(&c->ubits, stride * (uint64_t)c->B));
+    if (!c->unbits) HIPCHK(hipMalloc(&c->unbits, sizeof(uint64_t) * c->B));
+    if (!c->wbase) HIPCHK(hipMalloc(&c->wbase, sizeof(uint64_t) * c->B));
+    k_dec_refill<true><<<(unsigned)((c->B + kWavesPerBlock - 1) / kWavesPerBlock), 64 * kWavesPerBlock, 0, S(stream)>>>(
+        c->dec, bits_dev, stride_bytes, nbits_dev, base_words_dev, reinterpret_cast<uint64_t *>(c->ubits), c->cap_words,
+        c->unbits, c->wbase, c->B, c->prec);
+    CHECK_LAUNCH();
+    // a bad source left its count at ~0: k_dec_init fails that stream with the sticky LAC_E_ARG
+    const int rc = lac_decode_open(c, c->ubits, stride, c->unbits, stream);
+    if (rc) return rc;
+    c->wsrc = bits_dev;
+    c->wsrc_stride = stride_bytes;
+    c->wsrc_nbits = nbits_dev;
+    return LAC_OK;
+}
+
+int lac_decode_refill(lac_ctx *c, void *stream) {
+    if (!c) return fail(LAC_E_ARG, "ctx is NULL");
+    if (c->mode != 1 || !c->wsrc) return fail(LAC_E_STATE, "call lac_decode_open_window first");
+    HIPCHK(hipSetDevice(c->device));
+    k_dec_refill<false><<<(unsigned)((c->B + kWavesPerBlock - 1) / kWavesPerBlock), 64 * kWavesPerBlock, 0, S(stream)>>>(
+        c->dec, c->wsrc, c->wsrc_stride, c->wsrc_nbits, nullptr, reinterpret_cast<uint64_t *>(c->ubits), c->cap_words,
+        c->unbits, c->wbase, c->B, c->prec);
+    CHECK_LAUNCH();
+    return LAC_OK;
+}
+
+int lac_decode_window_base(lac_ctx *c, uint64_t *base_words_host, void *stream) {
+    if (!c || !base_words_host) return fail(LAC_E_ARG, "NULL argument");
+    if (c->mode != 1 || !c->wsrc) return fail(LAC_E_STATE, "call lac_decode_open_window first");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(base_words_host, c->wbase, sizeof(uint64_t) * c->B, hipMemcpyDeviceToHost, S(stream)));
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return LAC_OK;
 }
 
 static_assert(sizeof(lac_dec_state) == sizeof(DecState) && offsetof(lac_dec_state, ndet) == offsetof(DecState, ndet) &&

@@ -26,6 +26,11 @@ struct lac_ctx {
     const uint64_t *dnbits = nullptr;
     uint8_t *ubits = nullptr;           // lac_decode_open_packed: [B][cap_words * 8] unpacked slots and
     uint64_t *unbits = nullptr;         //                         [B] bit counts, allocated on first use
+    // lac_decode_open_window: ubits / unbits are the window and its counts (one open decode at a time)
+    const uint8_t *wsrc = nullptr;      //   the borrowed source k_dec_refill reads; null: the open decode has no window
+    uint64_t wsrc_stride = 0;
+    const uint64_t *wsrc_nbits = nullptr;
+    uint64_t *wbase = nullptr;          //   [B] source word that window word 0 holds, allocated on first use
     int mode = 0;                       // 0 encode, 1 decode
     int finished = 0;                   // nbits / planeA hold finished streams (a job, lac_encode_finish)
     int open = 0;                       // streams hold coded symbols since the last reset and are not

@@ -242,12 +242,15 @@ class LogitsCompressor:
       causal mask position t never depends on later ones, and equal shapes select
       the same kernels.  O(T) full forwards: for modules without a cache.
 
-    ``drain_every=N`` (incremental compress only): the coder is sized for N positions, not
+    ``drain_every=N`` (incremental modules only): the coder is sized for N positions, not
     for T -- ``N * (prec + 2) + 256`` bits plus ``DRAIN_KEEP_BITS`` for the words a drain
-    holds back -- and its settled output is drained to the host every N positions
-    (``lac_amd.batch.DrainSink``, include/lac.h lac_encode_drain), so the device memory of a
-    session no longer grows with its length.  The output is identical.  The teacher-forced
-    ``encode_logits_job`` path is one launch and does not drain: it is sized for T as before.
+    holds back -- on both sides.  compress drains its settled output to the host every N
+    positions (``lac_amd.batch.DrainSink``, include/lac.h lac_encode_drain); decompress keeps
+    the streams on the host (``lac_amd.batch.HostBits``) and slides a window of that size over
+    them, refilled every N positions (include/lac.h lac_decode_open_window,
+    lac_decode_refill).  Device memory no longer grows with the session on either side, and
+    the output is identical.  The teacher-forced ``encode_logits_job`` path is one launch and
+    does not drain, and its decompress does not window: both are sized for T as before.
     """
 
     DRAIN_KEEP_BITS = 32 * 64   # room for the kept words: a drain keeps <= 8 on the streams measured (a run of
@@ -362,16 +365,27 @@ class LogitsCompressor:
         -1, and an ended stream feeds the model BOS."""
         import torch
         B = len(data)
-        stride = max(8, (max((len(d) for d in data), default=0) + 8) // 8 * 8)
-        buf = np.zeros((B, stride), dtype=np.uint8)
-        for b, d in enumerate(data):
-            buf[b, :len(d)] = np.frombuffer(d, dtype=np.uint8)
-        coder = self._coder(B, T)
-        bits = torch.from_numpy(buf).to(self.device)
-        nb = torch.as_tensor(np.asarray(nbits, dtype=np.int64), device=self.device)
+        N = self.drain_every if self.incremental else None
+        src = None
+        if N is None:
+            stride = max(8, (max((len(d) for d in data), default=0) + 8) // 8 * 8)
+            buf = np.zeros((B, stride), dtype=np.uint8)
+            for b, d in enumerate(data):
+                buf[b, :len(d)] = np.frombuffer(d, dtype=np.uint8)
+            coder = self._coder(B, T)
+            bits = torch.from_numpy(buf).to(self.device)
+            nb = torch.as_tensor(np.asarray(nbits, dtype=np.int64), device=self.device)
+        else:
+            # the streams stay on the host; the coder holds a window sized for N positions
+            from .batch import HostBits
+            coder = self._coder(B, min(N, T), self.DRAIN_KEEP_BITS)
+            src = HostBits(data, nbits, self.device)
         if lengths is not None:
             coder.set_stream_lengths(self._lengths(lengths, B, T))
-        coder.decode_open(bits, nb)
+        if src is None:
+            coder.decode_open(bits, nb)
+        else:
+            coder.decode_open_window(src)
         out = torch.empty((B, T), dtype=torch.long, device=self.device)
         # the token fed back for a decoded -1 (a stream past its count; none without lengths,
         # where an error raises below): BOS -- the model needs an input, the coder ignores the row
@@ -379,6 +393,10 @@ class LogitsCompressor:
         if self.incremental:
             for t, lg in self._steps(B, T, lambda t: fed(out[:, t])):
                 out[:, t] = coder.decode_logits_step(lg)[0].to(torch.long)
+                if src is not None and (t + 1) % N == 0:
+                    coder.refill()
+            if src is not None:
+                coder.refill()                                   # (a stream that outran its window is found here)
         else:
             ctx = torch.zeros((B, T), dtype=torch.long, device=self.device)
             ctx[:, 0] = self.bos
@@ -388,6 +406,10 @@ class LogitsCompressor:
                 out[:, t] = s
                 if t + 1 < T:
                     ctx[:, t + 1] = fed(s)
-        coder.raise_on_error()
-        coder.close()
+        try:
+            coder.raise_on_error()                               # (synchronises: the refills have run)
+        finally:
+            coder.close()
+            if src is not None:
+                src.close()
         return out
