@@ -41,6 +41,31 @@
  *                       (the reference raises ZeroDivisionError, arith_code.py:307)
  *   LAC_E_FLUSH_LOOP    A_from_bin.flush emits symbols that leave [l, h]
  *                       unchanged (the reference loops forever, :308-313)
+ *
+ * The per-stream contract, the same on every encode and decode kernel form (path, straight or
+ * general block, job or separate calls, fused or split, windowed or not):
+ *   Precedence.  An encode step tests, in this order, the symbol's range (LAC_E_SYMBOL_RANGE),
+ *     the table (LAC_E_TABLE), a zero width at the symbol (LAC_E_ZERO_WIDTH) and, after the
+ *     narrowing, the output capacity (LAC_E_CAPACITY: a stream holds whole words,
+ *     ceil(capacity_bits / 64) + 1 of them, and fails at the first step whose digits pass them);
+ *     a step with several defects reports the first.  A decode step tests the table
+ *     (LAC_E_TABLE), then the registers (x outside [l, h]) and the decoded range
+ *     (LAC_E_DECODE_RANGE).
+ *   err_step is the stream's nsym at the failing symbol: symbols coded since the last
+ *     lac_encode_reset / lac_decode_open, whatever calls they came in -- a job cut into several
+ *     lac_encode or lac_decode_steps calls reports the step one call reports.  It is -1 while the
+ *     status is 0.  A stream whose flush does not fit (lac_encode_finish, or a job's finish) gets
+ *     LAC_E_CAPACITY with err_step = the symbols it holds; a stream refused at lac_decode_open
+ *     (LAC_E_ARG) has err_step 0.
+ *   Frozen.  A symbol, table or zero-width error, and every decode error, leaves the stream
+ *     exactly as it was before the failing step: registers, counters (nsym, L, pos, det / ndet),
+ *     plane words and trace entries (the failing step's and all later ones are not written).  A
+ *     capacity error happens after the narrowing: l, h and the plane registers are those of the
+ *     failing step, the same on every form, and nsym still excludes it.  From then on every
+ *     step is a no-op for the stream -- nothing of it depends on the symbols and rows it is given,
+ *     decode writes -1 to its sym_out entry, in this call and every later one --, lac_encode_finish
+ *     gives it 0 bits, and only lac_encode_reset (a job's included) / lac_decode_open clears the
+ *     status.  The other streams of the batch are not affected in any way.
  */
 #ifndef LAC_H
 #define LAC_H
@@ -387,9 +412,10 @@ int lac_flush_digits(lac_ctx *ctx, int8_t *digits_host, int32_t *count_host, voi
  * streams and capacity, so a job can stop after any lac_encode call and continue
  * later -- in this process or another -- bit for bit.  planes_host, when not NULL, is
  * [2][streams][cap_words] uint64 (plane A, then plane C; cap_words =
- * ceil(capacity_bits / 64)).  set refuses (LAC_E_ARG, nothing copied) register sets no
- * encoder reaches: l outside [0, 2^(prec+1)), h < l, h - l >= 2^prec, L beyond the
- * capacity, nflush outside [-1, 8] (streams with err set are copied as they are), and
+ * ceil(capacity_bits / 64) + 1, lac_encoded_device's stride_bytes / 8).  set refuses
+ * (LAC_E_ARG, nothing copied) register sets no encoder reaches: l outside
+ * [0, 2^(prec+1)), h < l, h - l >= 2^prec, L beyond the capacity, nflush outside
+ * [-1, 8] (streams with err set are copied as they are), and
  * planes_host == NULL while a stream has bits written (L > 0: its output words would
  * be whatever the context held); get and set refuse a decoding context (LAC_E_STATE;
  * lac_encode_reset first).  A restored context is not finished: lac_pack_bits needs a

@@ -408,7 +408,8 @@ __global__ LAC_ENC_BOUNDS void k_encode_fused(const E *__restrict__ pmf, int64_t
 #endif
         const int64_t s = sym[t * B + b];
         const RowSums rs = row_reduce_pf<E, VEC>(row, V, s, buf, next);
-        if (rs.T >> 64) { st.err = LAC_E_TABLE; break; }
+        // (coder_step's order, include/lac.h: the symbol's range before the table)
+        if (rs.T >> 64) { st.err = (s < 0 || s >= V) ? LAC_E_SYMBOL_RANGE : LAC_E_TABLE; break; }
         const uint64_t lo = (uint64_t)rs.lo;
         if (!coder_step<E>(st, l, h, lo, lo + rs.ps, (uint64_t)rs.T, rs.minp, s, row, V, prec, pa, pc, cap_words,
                            trace ? trace + 2 * (t * B + b) : nullptr, lane, mapping))

@@ -16,6 +16,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from conftest import REPO                                          # noqa: E402
+from errors import dec_state as _dec_state, set_dec_state as _set_dec_state   # noqa: E402
 from test_gpu_logits import _device_logits, _host_bits, _logits, _sample   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -66,20 +67,6 @@ def _padded(dl):
     buf = torch.full(dl.shape[:2] + (dl.shape[2] + n,), float("nan"), dtype=dl.dtype, device=dl.device)
     buf[..., :dl.shape[2]] = dl
     return buf[..., :dl.shape[2]]
-
-
-def _dec_state(c):
-    from lac_amd._lib import check
-    from lac_amd.coder import _DEC_STATE
-    st = np.zeros(c.streams, dtype=_DEC_STATE)
-    check(c.lib.lac_decode_get_state(c.ctx, st.ctypes.data_as(C.c_void_p), c._stream))
-    return st
-
-
-def _set_dec_state(c, st):
-    from lac_amd._lib import check
-    st = np.ascontiguousarray(st)
-    check(c.lib.lac_decode_set_state(c.ctx, st.ctypes.data_as(C.c_void_p), c._stream))
 
 
 def _written(ck):
