@@ -86,7 +86,7 @@ __host__ __device__ inline uint64_t div_floor_inv(u128 N, uint64_t d, double inv
 // above 2^64 (a quotient near 2^64 - 1, estimated high) starts from the largest
 // double below 2^64 instead, so the estimate stays within a few thousand of the
 // quotient and the second estimate leaves at most two +-1 corrections
-// (tests/test_core_host.py, also with the reciprocal 4 ULPs off).
+// (tests/test_core_host.py, also with the reciprocal 11 ULPs off, the device's worst).
 constexpr uint64_t kTopQ = 0xFFFFFFFFFFFFF800ull;
 
 // A remainder as a double: one rounding when it fits 64 bits (the split form
@@ -186,9 +186,14 @@ __host__ __device__ inline uint64_t f64_to_small(double e) {          // nearest
 // decoder's targets floor(v*T/w) and ranges ceil(c*w/T) at prec <= 50 with totals
 // below 2^50): one fused double estimate, fma(n, m, add) * inv rounded to the nearest
 // integer, is within q * (2^-52 + err(inv)) + 1/2 of the quotient -- under 2 for an
-// inv good to 2^-50 (the device reciprocal after its Newton step) -- so the remainder
-// n*m + add - q*d lies in (-3d, 3d) and wrapping 64-bit arithmetic holds it exactly;
-// at most two corrections follow.  No 128-bit products: the decode step's chain of
+// inv good to 2^-50 -- so the remainder n*m + add - q*d lies in (-3d, 3d) and wrapping
+// 64-bit arithmetic holds it exactly; at most two corrections follow.  The device
+// reciprocal after one Newton step (recip, recip_small) is not that good everywhere: never
+// above the correctly rounded 1/d, but up to 10 * 2^-52 below it at divisors just under a
+// power of two (measured on the MI355X, tests/test_gpu_arith.py, profiles/devarith/), so
+// the estimate of a quotient past 2^49 can be 3 below it.  div_small_fix's loops take that;
+// div_small_fix_mask does not, and its callers pass 1/d after two Newton steps
+// (recip2_small, within an ulp: the estimate within one).  No 128-bit products: the decode step's chain of
 // quarter-rate multiplies (div_floor_inv: two estimates and 128-bit remainders)
 // becomes one FMA, one multiply and a 64-bit remainder.
 constexpr uint64_t kSmallQuot = 1ull << 50;

@@ -438,7 +438,11 @@ __device__ inline int decode_symbol(DecState &st, const E *row, int64_t V, uint6
         uint64_t tgt, thi;                                    // targets of the 0- and 1-padded ends
         const bool small = UNI && T < kSmallQuot && prec <= 50;   // uniform
         if (small) {
-            const double iw = recip(w);
+            // (1/w and 1/T below with two Newton steps: with recip's one, up to 10 * 2^-52 low at
+            // divisors just under a power of two, the estimate of a quotient near 2^50 came out 3
+            // below it, past div_small_fix_mask's range -- a wrong symbol at prec 49-50,
+            // tests/test_gpu_arith.py, profiles/devarith/)
+            const double iw = recip2_small(w);                    // (w <= 2^50: exact as a double)
             tgt = div_small_u(v, T, 0, w, iw);
             thi = vhi == v ? tgt : (vhi < w ? div_small_u(vhi, T, 0, w, iw) : 0);
         } else {
@@ -456,7 +460,7 @@ __device__ inline int decode_symbol(DecState &st, const E *row, int64_t V, uint6
         s = cv0 * VEC + (int64_t)cnt;
         const uint64_t add = mapping == LAC_MAP_FLOOR ? 0 : T - 1;
         if (small) {
-            div_small_u2(lo_c, hi_c, w, add, T, recip(T), &a, &bb);
+            div_small_u2(lo_c, hi_c, w, add, T, recip2_small(T), &a, &bb);
         } else {
             div_pair(lo_c, hi_c, w, add, T, recip(T), &a, &bb);
         }
