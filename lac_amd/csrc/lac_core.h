@@ -24,19 +24,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#ifndef LAC_PLANE_FAST
-#define LAC_PLANE_FAST 1     // plane_append: the within-one-word case without the loop
-#endif
-#ifndef LAC_ENC_STRAIGHT
-#define LAC_ENC_STRAIGHT 1   // k_encode: 64-step blocks without per-step tests where no step can need one
-#endif
-#ifndef LAC_ENC_PIPE
-#define LAC_ENC_PIPE 1       // k_encode straight blocks: the next step's row values read one step ahead
-#endif
-#ifndef LAC_ENC_UNROLL
-#define LAC_ENC_UNROLL 2     // k_encode straight blocks: steps per loop iteration
-#endif
-
 namespace lac {
 
 typedef unsigned __int128 u128;
@@ -462,7 +449,6 @@ template <typename Store>
 __host__ __device__ inline bool plane_append(uint64_t &L, uint64_t &wa, uint64_t &wc, int k, uint64_t E,
                                              uint64_t cap_words, Store store) {
     if (k <= 0) return true;
-#if LAC_PLANE_FAST
     // the common case: the digits land inside the word bit L-1 is in (no word completes,
     // so no store and no loop), the carry on that word's bit L-1.  Bit L-1 stays in the
     // same word, which is within capacity: an earlier append put it there, or a restored
@@ -474,7 +460,6 @@ __host__ __device__ inline bool plane_append(uint64_t &L, uint64_t &wa, uint64_t
         L += (uint64_t)k;
         return true;
     }
-#endif
     const uint64_t ehi = E >> k;
     uint64_t elo = E & ((k == 64) ? ~0ull : ((1ull << k) - 1));
     if (ehi) wc |= 1ull << (63 - ((L - 1) & 63));         // carry onto bit L-1 (L >= 1 here)

@@ -289,10 +289,7 @@ __device__ inline int decode_advance(DecState &st, uint64_t a, uint64_t bb, cons
     return 0;
 }
 
-#ifndef LAC_Q1D_NB
-#define LAC_Q1D_NB 1             // k_q1_decode and k_decode_seq: decode_advance_nb (no renormalisation branches)
-#endif
-// decode_advance<true> with no branch past its range test (k_q1_decode, LAC_Q1D_NB):
+// decode_advance<true> with no branch past its range test (k_q1_decode, k_q1_step_dec, k_decode_seq):
 // renorm()'s kk <= 0 case as kk = 0 (e = 0 keeps the registers), window_bits_nb.
 __device__ inline int decode_advance_nb(DecState &st, uint64_t a, uint64_t bb, const BitWin &win, uint64_t nbits,
                                         int prec) {
@@ -332,14 +329,11 @@ __device__ unsigned long long g_dec_phase[8];
 __device__ inline bool neg_u(uint64_t r) { return (int64_t)r < 0; }
 
 // div_small_fix for wave-uniform values (|r| < 3d < 2^53).
-#ifndef LAC_DIVFIX_MASK
-#define LAC_DIVFIX_MASK 1        // div_small_fix_u as sign masks (lac_core.h div_small_fix_mask), no loops
-#endif
-// MASK: the branch-free correction -- for the lone-wave chains (k_decode_lean, k_decode_seq:
+// MASK: the branch-free correction as sign masks (lac_core.h div_small_fix_mask), no loops -- for the lone-wave chains (k_decode_lean, k_decode_seq:
 // c2 decode 1.253 -> 1.229 us per step); k_q1_decode, whose 16 stream-waves per CU hide the
 // loops' branches, keeps the loops (the masks' extra instructions: 4.3 -> 4.6 us per bf16 c3
 // step; profiles/r05/straight/)
-template <bool MASK = LAC_DIVFIX_MASK>
+template <bool MASK = true>
 __device__ inline uint64_t div_small_fix_u(uint64_t q, uint64_t n, uint64_t m, uint64_t add, uint64_t d) {
     if constexpr (MASK) return div_small_fix_mask(q, n, m, add, d);
     uint64_t r = n * m + add - q * d;
@@ -357,13 +351,13 @@ __device__ inline uint64_t div_small_fix_u(uint64_t q, uint64_t n, uint64_t m, u
 
 // div_small with wave-uniform arguments: the double estimate on the vector unit (the
 // SALU has no FP64), read back, the 64-bit remainder and its corrections on the SALU.
-template <bool MASK = LAC_DIVFIX_MASK>
+template <bool MASK = true>
 __device__ inline uint64_t div_small_u(uint64_t n, uint64_t m, uint64_t add, uint64_t d, double inv) {
     return div_small_fix_u<MASK>(rfl_u64(div_small_est(n, m, add, inv)), n, m, add, d);
 }
 // Two of them with one divisor (the ranges ceil(lo*w/T), ceil(hi*w/T)): both estimates
 // first, so the two FP64 chains overlap, then both corrections.
-template <bool MASK = LAC_DIVFIX_MASK>
+template <bool MASK = true>
 __device__ inline void div_small_u2(uint64_t n0, uint64_t n1, uint64_t m, uint64_t add, uint64_t d, double inv,
                                     uint64_t *q0, uint64_t *q1) {
     const uint64_t e0 = rfl_u64(div_small_est(n0, m, add, inv)), e1 = rfl_u64(div_small_est(n1, m, add, inv));
@@ -483,8 +477,7 @@ __device__ inline int decode_symbol(DecState &st, const E *row, int64_t V, uint6
     else st.det = 0;
     *s_out = s;
     // (UNI, the lone-wave k_decode_seq: the renormalisation without branches, as k_q1_decode)
-    const int rc = (UNI && LAC_Q1D_NB) ? decode_advance_nb(st, a, bb, win, nbits, prec)
-                                        : decode_advance<UNI>(st, a, bb, win, nbits, prec);
+    const int rc = UNI ? decode_advance_nb(st, a, bb, win, nbits, prec) : decode_advance<UNI>(st, a, bb, win, nbits, prec);
     mark(5);
     return rc;
 }

@@ -321,11 +321,6 @@ __device__ inline uint64_t wave_sum8_u64(const uint64_t (&s)[8], uint32_t &ovf) 
     return r;
 }
 
-#ifndef LAC_DEC_XPF                // k_decode_wave_fine: next group in flight while one is consumed,
-                                   // and the next row's first group over the step's tail (+2.5 %)
-#define LAC_DEC_XPF 1
-#endif
-
 // k_decode_wave with one total per 64-vector iteration of the row instead of per
 // <= 64-iteration chunk (rows of <= 512 iterations: V <= 131072 u32 / 65536 u64
 // entries).  Iteration p's total lives in lane p % 64 of register p / 64, the
@@ -333,7 +328,7 @@ __device__ inline uint64_t wave_sum8_u64(const uint64_t (&s)[8], uint32_t &ovf) 
 // load per lane (1 KB, 0.8 % of a 32000-entry u32 row) instead of a chunk of
 // eight (6.3 %), which also shortens the dependent tail of every step.
 template <typename E, int VEC, int NR>
-__global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wave_fine(const E *__restrict__ pmf, int64_t step_stride,
+__global__ __launch_bounds__(64 * kStreamWaves, kDecFineMinWaves) void k_decode_wave_fine(const E *__restrict__ pmf, int64_t step_stride,
                                                   int64_t stream_stride, int64_t nsteps, int64_t V, int prec,
                                                   DecState *states, const uint8_t *bits, uint64_t stride,
                                                   const uint64_t *nbits, int32_t *sym_out, int64_t B, int mapping,
@@ -353,25 +348,16 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
         nsteps = live_steps(slen, b, st.nsym, nall);
         for (int64_t j = nsteps + lane; j < nall; j += 64) sym_out[j * B + b] = -1;
     }
-#if LAC_DEC_XPF
-    // XD = 2: two groups in flight (g + 1 and g + 2) while group g is summed, and the
-    // next row's groups 0 and 1 over the step's tail; rows of <= 128 iterations (u64:
-    // <= 256) only (240-250 VGPRs; longer u32 rows' second buffer spilled)
-    constexpr int XD = (LAC_DEC_XPF >= 2 && (NR <= 2 || (W && NR <= 4))) ? 2 : 1;
-    typename VecT<E, VEC>::type xb[8], xb2[8];
+    // The next group in flight while one is consumed, and the next row's first group over
+    // the step's tail (+2.5 %).  (Two groups in flight through a second buffer, 240-250
+    // VGPRs, measured no faster, profiles/r03/xpf2_rejected/: removed in this commit.)
+    typename VecT<E, VEC>::type xb[8];
     if (nsteps > 0) {
         const E *row0 = pmf + b * stream_stride;
 #pragma unroll
         for (int u = 0; u < 8; u++)
             xb[u] = nvec >= 512 ? load_vec<E, VEC>(row0, u * 64 + lane) : load_vec_or0<E, VEC>(row0, u * 64 + lane, nvec);
-        if (XD == 2 && ngrp > 1) {
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                xb2[u] = nvec >= 1024 ? load_vec<E, VEC>(row0, (8 + u) * 64 + lane)
-                                      : load_vec_or0<E, VEC>(row0, (8 + u) * 64 + lane, nvec);
-        }
     }
-#endif
     for (int64_t t = 0; t < nsteps; t++) {
         int32_t *out = sym_out + t * B + b;
         if (st.err) {
@@ -387,33 +373,19 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
                                                               // (a lane at 2^32 - 1 already means T >= 2^64)
         uint32_t ovf = 0;                                     // (unused: totals wrap, see u64_total_overflows)
         const int nfull = nvec / 512;                         // groups of 8 whole iterations
-        auto group = [&](int g, bool full) {
-#if LAC_DEC_XPF
+        auto group = [&](int g) {
             // x holds group g (issued after group g-1, or before the previous step's tail)
             typename VecT<E, VEC>::type x[8];
 #pragma unroll
             for (int u = 0; u < 8; u++) x[u] = xb[u];
-            if constexpr (XD == 2) {
-#pragma unroll
-                for (int u = 0; u < 8; u++) xb[u] = xb2[u];
-            }
-            auto &nb = XD == 2 ? xb2 : xb;                    // group g + XD into the freed buffer
-            if (g + XD < ngrp) {
-                const bool nf = g + XD < nfull;
+            if (g + 1 < ngrp) {                               // group g + 1 into the freed buffer
+                const bool nf = g + 1 < nfull;
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
-                    const int vi = ((g + XD) * 8 + u) * 64 + lane;
-                    nb[u] = nf ? load_vec<E, VEC>(row, vi) : load_vec_or0<E, VEC>(row, vi, nvec);
+                    const int vi = ((g + 1) * 8 + u) * 64 + lane;
+                    xb[u] = nf ? load_vec<E, VEC>(row, vi) : load_vec_or0<E, VEC>(row, vi, nvec);
                 }
             }
-#else
-            typename VecT<E, VEC>::type x[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int vi = (g * 8 + u) * 64 + lane;
-                x[u] = full ? load_vec<E, VEC>(row, vi) : load_vec_or0<E, VEC>(row, vi, nvec);
-            }
-#endif
             uint64_t s[8];
 #pragma unroll
             for (int u = 0; u < 8; u++) {
@@ -439,9 +411,8 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
             for (int r = 0; r < NR; r++)
                 if (r == (g >> 3) && mylane) mine[r] = tot;
         };
-        for (int g = 0; g < nfull; g++) group(g, true);
-        if (nfull < ngrp) group(nfull, false);
-#if LAC_DEC_XPF
+        for (int g = 0; g < nfull; g++) group(g);
+        if (nfull < ngrp) group(nfull);
         if (t + 1 < nsteps) {                                 // next row's group 0, in flight over the tail
             const E *nrow = row + step_stride;
 #pragma unroll
@@ -449,15 +420,7 @@ __global__ __launch_bounds__(64 * LAC_STREAM_WG, LAC_DECF_MINW) void k_decode_wa
                 const int vi = u * 64 + lane;
                 xb[u] = nfull > 0 ? load_vec<E, VEC>(nrow, vi) : load_vec_or0<E, VEC>(nrow, vi, nvec);
             }
-            if (XD == 2 && ngrp > 1) {                        // and its group 1
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int vi = (8 + u) * 64 + lane;
-                    xb2[u] = nfull > 1 ? load_vec<E, VEC>(nrow, vi) : load_vec_or0<E, VEC>(nrow, vi, nvec);
-                }
-            }
         }
-#endif
         uint64_t incl[NR];
         uint64_t base = 0;
 #pragma unroll
@@ -973,9 +936,6 @@ constexpr int kLeanAhead = LAC_LEAN_AHEAD;      // rows prefetched ahead of the 
 #endif
 constexpr int kLeanPub = LAC_LEAN_PUB;          // the decoder publishes its progress every kLeanPub steps
 // (kLeanHelpers, kLeanMaxStreams, kLeanHelpMaxStreams, kLeanBytes, kLeanRounds: lac_select.h)
-#ifndef LAC_LEAN_WIDE_WINDOW
-#define LAC_LEAN_WIDE_WINDOW 1                  // wide u64 rows: the search against a double window
-#endif
 
 __device__ inline int32_t lean_progress(const int32_t *p) {
     return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -1224,7 +1184,7 @@ __global__ __launch_bounds__(64) void k_decode_lean(const E *__restrict__ lcdf, 
         // (u64 rows of 2^50 and more: no exact target -- by div_floor_inv's two estimates and
         // 128-bit remainders in the loads' shadow it measured slower, 1.775 vs 1.70 us per c2
         // step, profiles/r06/lean/ -- but the window below: 1.418 vs 1.442 us with products
-        // alone, profiles/r06/lean3/widewindow/)
+        // alone, profiles/r06/lean3/widewindow/; the products-alone search removed in this commit)
         const E te = (!W || small) ? (E)div_near_u(vs, Ts, 0, ws, iw) : (E)0;
         // u64 rows of 2^50 and more: a window [tlo, thi] around v*T/w from doubles that holds
         // the target -- v exact, T within an ulp, 1/w to ~2^-50 (one Newton step), so the
@@ -1291,7 +1251,6 @@ __global__ __launch_bounds__(64) void k_decode_lean(const E *__restrict__ lcdf, 
             kL = (uint32_t)__builtin_amdgcn_readlane((int)k, L);
         };
         if (!W || small) search([&](E c) { return c <= te; });
-        else if (!LAC_LEAN_WIDE_WINDOW) search([&](E c) { return le((uint64_t)c); });
         else {
             search([&](E c) { return (uint64_t)c <= tlo; });
             auto inw = [&](uint64_t c) { return (c > tlo) & (c <= thi); };

@@ -35,40 +35,19 @@ using namespace lac;
 
 #define LAC_VERSION "lac-mi355x 0.1 (gfx950)"
 
-// Row-scan tuning (tools/tune_encode.sh builds variants): vectors in flight per
-// lane, and nontemporal (read-once) vs default cache policy on the row loads.
-#ifndef LAC_UNROLL
-#define LAC_UNROLL 8
-#endif
-#ifndef LAC_NT
-#define LAC_NT 1
-#endif
-// Minimum waves per SIMD for the one-wave-per-stream kernels (0 = no bound).
-// With 4096 streams every stream's wave is resident at 4 waves/SIMD; the
-// register cap spills only a few values of the per-step tail, never the row loop.
-#ifndef LAC_ENC_MINW
-#define LAC_ENC_MINW 0
-#endif
-#ifndef LAC_DEC_MINW
-#define LAC_DEC_MINW 4
-#endif
+namespace {
+
+// Row scan: vectors in flight per lane.  The row loads are nontemporal (rows are read once).
+constexpr int kUnroll = 8;
+// Minimum waves per SIMD for k_decode_wave and k_q1_decode.  With 4096 streams every
+// stream's wave is resident at 4 waves/SIMD; the register cap spills only a few values of
+// the per-step tail, never the row loop.  (k_encode_fused carries no such bound.)
+constexpr int kDecMinWaves = 4;
 // k_decode_wave_fine: 2 waves/SIMD (no spills, two balanced rounds of 2048
 // stream-waves at 4096 streams) measured +2.5 % over 4 (6.54 -> 6.70 TB/s).
-#ifndef LAC_DECF_MINW
-#define LAC_DECF_MINW 2
-#endif
-#if LAC_ENC_MINW > 0
-#define LAC_ENC_BOUNDS __launch_bounds__(64 * LAC_STREAM_WG, LAC_ENC_MINW)
-#else
-#define LAC_ENC_BOUNDS __launch_bounds__(64 * LAC_STREAM_WG)
-#endif
-#if LAC_DEC_MINW > 0
-#define LAC_DEC_BOUNDS __launch_bounds__(256, LAC_DEC_MINW)
-#else
-#define LAC_DEC_BOUNDS __launch_bounds__(256)
-#endif
-
-namespace {
+constexpr int kDecFineMinWaves = 2;
+#define LAC_ENC_BOUNDS __launch_bounds__(64 * kStreamWaves)
+#define LAC_DEC_BOUNDS __launch_bounds__(256, kDecMinWaves)
 
 constexpr int kChunkSteps = 64;       // split path: steps per row-stats launch at >= 512 streams
 constexpr int kWavesPerBlock = 4;     // 256-thread workgroups
@@ -76,10 +55,7 @@ constexpr int kWavesPerBlock = 4;     // 256-thread workgroups
 // 1 or 2 (a finished wave's slot refilled without waiting for its workgroup's
 // slowest wave) measured no faster: c3 / c4 / u64 encode and decode within noise,
 // u64 decode 13 % slower at 2 (profiles/r02/stream_wg_rejected/)
-#ifndef LAC_STREAM_WG
-#define LAC_STREAM_WG 4
-#endif
-constexpr int kStreamWaves = LAC_STREAM_WG;
+constexpr int kStreamWaves = 4;
 
 // ------------------------------------------------------------------ wave helpers
 __device__ inline uint32_t lane_id() { return __lane_id(); }
@@ -281,11 +257,7 @@ template <> struct VecT<uint64_t, 1> { typedef uint64_t type; };
 template <typename E, int VEC>
 __device__ inline typename VecT<E, VEC>::type load_vec(const E *row, int64_t vi) {
     typedef typename VecT<E, VEC>::type V;
-#if LAC_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const V *>(row) + vi);
-#else
-    return reinterpret_cast<const V *>(row)[vi];
-#endif
+    return __builtin_nontemporal_load(reinterpret_cast<const V *>(row) + vi);   // rows are read once
 }
 template <typename E, int VEC>
 __device__ inline E vget(const typename VecT<E, VEC>::type &v, int j) {
@@ -323,7 +295,7 @@ __device__ inline RowSums row_reduce(const E *row, int64_t V, int64_t s) {
     constexpr bool W = sizeof(E) == 8;
     uint64_t tot = 0, lo = 0, tot_h = 0, lo_h = 0, ps = 0;     // *_h: high halves (u64 rows)
     E mn = (E)~(E)0;                                          // min over (x - 1): 0 wraps to max
-    constexpr int U = LAC_UNROLL;
+    constexpr int U = kUnroll;
     auto take = [&](const typename VecT<E, VEC>::type &x, int64_t v) {
         uint64_t sl = 0, sh = 0;
 #pragma unroll
@@ -380,30 +352,22 @@ __device__ inline RowSums row_reduce(const E *row, int64_t V, int64_t s) {
     return r;
 }
 
-// The same reduction, software-pipelined across groups and rows.  A row is
-// streamed in groups of U = LAC_UNROLL vectors per lane; `buf` holds the group
-// being consumed while the next one is in flight (LAC_PIPE 1: the next group's
-// loads are issued before the current group is consumed, 2 x U vectors in
-// registers; LAC_PIPE 0: issued right after it).  After the row's last group,
-// `next` (the wave's following row, or nullptr) gets its first group issued, so
-// the per-step tail -- wave reductions, the coder step -- runs with loads in
-// flight instead of with the wave's memory pipe idle.  On entry `buf` must hold
-// group 0 of `row` (row_group_load(buf, row, 0, nvec)).
-#ifndef LAC_PIPE
-#define LAC_PIPE 0
-#endif
-// Measured on MI355X (same box, c3): no gain for the fused encoder -- u32
-// 1.214 (off) vs 1.219 ms/job, u64 2.43 (off) vs 2.50 ms with a 2-wave bound
-// (3.07 ms unbounded: one wave per SIMD) -- so it is off by default; the
-// decoder, whose tail holds a dependent re-read, gains (LAC_DEC_XPF).
-#ifndef LAC_XPF                    // issue the next row's first group before the step's tail
-#define LAC_XPF 0
-#endif
-template <typename E, int VEC> struct RowGroup { typename VecT<E, VEC>::type x[LAC_UNROLL]; };
+// The same reduction over a row streamed in groups of U = kUnroll vectors per lane: `buf`
+// holds the group being consumed, and the next group's loads are issued right after it.
+// On entry `buf` must hold group 0 of `row` (row_group_load(buf, row, 0, nvec)).
+// Two variants, removed in this commit: the next group's loads issued before the current
+// group is consumed (2 x U vectors in registers), and the following row's first group
+// issued before the step's tail.  Measured on MI355X (same box, c3): no gain for the fused
+// encoder -- u32 1.214 (off) vs 1.219 ms/job, u64 2.43 (off) vs 2.50 ms with a 2-wave bound
+// (3.07 ms unbounded: one wave per SIMD); the decoder, whose tail holds a dependent
+// re-read, gains (k_decode_wave_fine's own prefetch).
+// (A deliberate copy of row_reduce: one accumulator struct shared by the two changes every
+// k_encode_fused and k_row_stats instance.)
+template <typename E, int VEC> struct RowGroup { typename VecT<E, VEC>::type x[kUnroll]; };
 
 template <typename E, int VEC>
 __device__ inline void row_group_load(RowGroup<E, VEC> &g, const E *row, int64_t base, int64_t nvec) {
-    constexpr int U = LAC_UNROLL;
+    constexpr int U = kUnroll;
     const int64_t vi = base + (int64_t)lane_id();
     if (base + 64 * U <= nvec) {                              // wave-uniform: the whole group is in the row
 #pragma unroll
@@ -415,13 +379,13 @@ __device__ inline void row_group_load(RowGroup<E, VEC> &g, const E *row, int64_t
 }
 
 template <typename E, int VEC>
-__device__ inline RowSums row_reduce_pf(const E *row, int64_t V, int64_t s, RowGroup<E, VEC> &buf, const E *next) {
+__device__ inline RowSums row_reduce_pf(const E *row, int64_t V, int64_t s, RowGroup<E, VEC> &buf) {
     const int lane = (int)lane_id();
     const int64_t sc = s < 0 ? 0 : (s > V ? V : s);
     const int64_t nvec = V / VEC, sfull = sc / VEC;
     const int sr = (int)(sc - sfull * VEC);
     constexpr bool W = sizeof(E) == 8;
-    constexpr int U = LAC_UNROLL;
+    constexpr int U = kUnroll;
     uint64_t tot = 0, lo = 0, tot_h = 0, lo_h = 0, ps = 0;
     E mn = (E)~(E)0;
     auto take = [&](const typename VecT<E, VEC>::type &x, int64_t v) {
@@ -450,18 +414,9 @@ __device__ inline RowSums row_reduce_pf(const E *row, int64_t V, int64_t s, RowG
     const int64_t gw = 64 * U, ngrp = (nvec + gw - 1) / gw;
     for (int64_t g = 0; g < ngrp; g++) {
         const int64_t base = g * gw;
-#if LAC_PIPE
-        const RowGroup<E, VEC> cur = buf;
-        if (g + 1 < ngrp) row_group_load<E, VEC>(buf, row, base + gw, nvec);
-        else if (next) row_group_load<E, VEC>(buf, next, 0, nvec);
-#pragma unroll
-        for (int u = 0; u < U; u++) take(cur.x[u], base + 64 * u + lane);
-#else
 #pragma unroll
         for (int u = 0; u < U; u++) take(buf.x[u], base + 64 * u + lane);
         if (g + 1 < ngrp) row_group_load<E, VEC>(buf, row, base + gw, nvec);
-        else if (next) row_group_load<E, VEC>(buf, next, 0, nvec);
-#endif
     }
     RowSums r;
     tot = wave_sum_u64(tot);

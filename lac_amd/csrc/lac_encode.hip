@@ -28,7 +28,6 @@ namespace {
 #if LAC_ENC_PHASES
 __device__ unsigned long long g_enc_phase[8];
 #endif
-constexpr int kEncUnroll = LAC_ENC_UNROLL;
 
 // ------------------------------------------------------------------ split path
 // k_row_stats: one wave per (step, stream) row -> RowStats.  Fully parallel over
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(256) void k_row_stats(const E *__restrict__ pmf, in
 }
 
 // k_encode's straight steps over one 64-step block (see k_encode): step i's row values
-// out of lane i (LAC_ENC_PIPE: read one step ahead, off the chain), the two mul-divs
+// out of lane i (read one step ahead, off the chain), the two mul-divs
 // through the row fractions (T32: 32 x 64-bit remainder products), renorm() without its
 // kk <= 0 branch (kk = 0 keeps l and h, e = 0), plane_append's one-word case inline.  The
 // inner loop leaves only at the block's end, at a step whose digits cross a plane word
@@ -114,8 +113,8 @@ __device__ inline int straight_steps(const SP &sp, EncState &st, int64_t &l, int
     bool fudged = false;
     while (i < n) {
         for (; i < n; i++) {
-            const Row r = LAC_ENC_PIPE ? nx : rd(i);
-            if constexpr (LAC_ENC_PIPE) nx = rd(i + 1 < n ? i + 1 : i);
+            const Row r = nx;
+            nx = rd(i + 1 < n ? i + 1 : i);
             const uint64_t w = (uint64_t)(h - l + 1);
             if constexpr (FT) {
                 if (!nonneg_uni((int64_t)(w - r.ft))) {         // fudged (arith_code.py:84): the general step
@@ -220,7 +219,6 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
         const uint64_t flo = frac_ok ? row_frac(my.lo, my.tot) : kNoFrac;
         const uint64_t fhi = frac_ok ? row_frac(my.hi, my.tot) : kNoFrac;
         int i0 = 0;                                       // the first step the general loop takes
-#if LAC_ENC_STRAIGHT
         if constexpr (sizeof(E) == 8) {
             // u64 tables: the straight form of straight_steps -- every step's row with
             // 0 < T < 2^62, a positive width at the symbol (for the floor mapping also
@@ -262,6 +260,7 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
         // step two mul-divs in 32 x 64-bit products, a branch-free renormalisation and the
         // plane append's one-word case, one rarely taken branch (the append crossing a
         // word).  Results, registers and error steps are coder_step's.
+        // (A deliberate copy of straight_steps<CEIL, true, false>: calling it here changes all four k_encode instances.)
         if (i0 == 0) {
             const uint64_t half = 1ull << (prec - 1);
             const bool lfast = lane >= n || (frac_ok && my.tot != 0 && my.tot <= half && !(my.tot >> 32) &&
@@ -274,8 +273,8 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
                 auto store = [&](uint64_t idx, uint64_t wa, uint64_t wc) {
                     if (lane == 0) { pa[idx] = wa; pc[idx] = wc; }
                 };
-                // step i's row values out of lane i (LAC_ENC_PIPE: read one step ahead, so
-                // the readlanes' latency is not on the chain)
+                // step i's row values out of lane i (read one step ahead, so the readlanes'
+                // latency is not on the chain)
                 auto rd = [&](int j, uint32_t &lo, uint32_t &hi, uint32_t &T, uint64_t &fl, uint64_t &fh) {
                     lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my.lo, j);
                     hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my.hi, j);
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
                 };
                 uint32_t nlo, nhi, nT;
                 uint64_t nfl, nfh;
-                if constexpr (LAC_ENC_PIPE) rd(0, nlo, nhi, nT, nfl, nfh);
+                rd(0, nlo, nhi, nT, nfl, nfh);
                 int i = 0;
                 int kk = 0;
                 uint64_t e = 0;
@@ -296,12 +295,8 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
                     for (; i < n; i++) {
                         uint32_t lo, hi, T;
                         uint64_t fl, fh;
-                        if constexpr (LAC_ENC_PIPE) {
-                            lo = nlo, hi = nhi, T = nT, fl = nfl, fh = nfh;
-                            rd(i + 1 < n ? i + 1 : i, nlo, nhi, nT, nfl, nfh);
-                        } else {
-                            rd(i, lo, hi, T, fl, fh);
-                        }
+                        lo = nlo, hi = nhi, T = nT, fl = nfl, fh = nfh;
+                        rd(i + 1 < n ? i + 1 : i, nlo, nhi, nT, nfl, nfh);
                         const uint64_t w = (uint64_t)(h - l + 1);
                         const uint64_t a = frac_mul_div32<CEIL>(fl, lo, w, T), bb = frac_mul_div32<CEIL>(fh, hi, w, T);
                         h = l + (int64_t)bb - 1;
@@ -333,7 +328,6 @@ __global__ __launch_bounds__(256) void k_encode(const RowStats *__restrict__ sta
                 continue;
             }
         }
-#endif
         uint64_t fthr = lane < n && my.minp ? div_floor((u128)my.tot + (my.minp - 1), my.minp) : 0;
         fthr = fthr < (1ull << 62) ? fthr : (1ull << 62);   // w <= 2^61: w < fthr unchanged (coder_step's sign test)
         if (clk) clk->mark(4);
@@ -396,18 +390,12 @@ __global__ LAC_ENC_BOUNDS void k_encode_fused(const E *__restrict__ pmf, int64_t
     }
     int64_t l = st.l, h = st.h;
     RowGroup<E, VEC> buf;
-    if (LAC_XPF && nsteps > 0) row_group_load<E, VEC>(buf, pmf + t0 * step_stride + b * stream_stride, 0, V / VEC);
     for (int64_t i = 0; i < nsteps; i++) {
         const int64_t t = t0 + i;
         const E *row = pmf + t * step_stride + b * stream_stride;
-#if LAC_XPF
-        const E *next = i + 1 < nsteps ? row + step_stride : nullptr;
-#else
-        const E *next = nullptr;
         row_group_load<E, VEC>(buf, row, 0, V / VEC);
-#endif
         const int64_t s = sym[t * B + b];
-        const RowSums rs = row_reduce_pf<E, VEC>(row, V, s, buf, next);
+        const RowSums rs = row_reduce_pf<E, VEC>(row, V, s, buf);
         // (coder_step's order, include/lac.h: the symbol's range before the table)
         if (rs.T >> 64) { st.err = (s < 0 || s >= V) ? LAC_E_SYMBOL_RANGE : LAC_E_TABLE; break; }
         const uint64_t lo = (uint64_t)rs.lo;

@@ -18,26 +18,12 @@ namespace {
 // reductions (the row is re-read while it is still resident in the 256 MB MALL).
 __constant__ uint32_t c_q1_tab[LAC_Q1_TAB_SIZE] = LAC_Q1_TAB_INIT;
 
-#ifndef LAC_Q1_NT
-#define LAC_Q1_NT 1              // logits rows are read once: nontemporal loads
-#endif
-// the LDS-DMA loads of the register + slot shapes with the nt policy too: a DMA
-// stream without it read at 76.5 % of peak, with it 86 % = the register loads'
-// (tools/hbm_probe3.hip, profiles/r03/hbm_probe3.txt)
-#ifndef LAC_Q1_DMA_NT
-#define LAC_Q1_DMA_NT LAC_Q1_NT
-#endif
-#if LAC_Q1_DMA_NT
-#define LAC_Q1_DMA_POLICY " nt"
-#else
-#define LAC_Q1_DMA_POLICY ""
-#endif
-#ifndef LAC_Q1_DEC_DIRECT
-#define LAC_Q1_DEC_DIRECT 1      // k_q1_stats decode form, one row per block of 64 groups: per-wave chunk stores
-#endif
-#ifndef LAC_Q1_SCHED
-#define LAC_Q1_SCHED 0           // scheduling fence between vectors in k_q1_stats
-#endif
+// Logits rows are read once: every row load is nontemporal.  The LDS-DMA loads of the
+// register + slot shapes carry the nt policy too: a DMA stream without it read at 76.5 %
+// of peak, with it 86 % = the register loads' (tools/hbm_probe3.hip, profiles/r03/hbm_probe3.txt)
+
+// Kept as a switch on purpose: deleting this never-compiled branch (pend_*, flush_pending in
+// k_q1_stats) reorders the four DIRECT decode instances of k_q1_stats (profiles/isa/README.md).
 #ifndef LAC_Q1_DEFER_DEC
 #define LAC_Q1_DEFER_DEC 0       // k_q1_stats decode form: a row's chunk stores after the next row's max
                                  // (measured: 3 VGPRs spilled, decode stats 42.1 -> 42.7 us per bf16 c3
@@ -51,9 +37,6 @@ __device__ inline s16x2 as_s16x2(uint32_t w) {
     __builtin_memcpy(&r, &w, 4);
     return r;
 }
-#ifndef LAC_Q1_IMAX
-#define LAC_Q1_IMAX 1            // bf16 row max on packed int16 bit patterns (k_q1_stats)
-#endif
 
 template <typename LT> struct LogitN { static constexpr int N = 16 / sizeof(LT); };
 
@@ -118,9 +101,6 @@ __device__ inline uint32_t q1_val(float x, float c, const uint32_t *tab) { retur
 #define LAC_Q1_MINW 4            // k_q1_stats launch bound: waves per SIMD
 #endif
 constexpr int kQ1Rep = LAC_Q1_REP;
-#ifndef LAC_Q1_FASTFILL
-#define LAC_Q1_FASTFILL 1        // replicated-table fill: loads first, 16-B LDS writes
-#endif
 template <int REP = kQ1Rep>
 __device__ inline void q1_load_tab_rep(uint32_t *tabr, uint32_t xsh) {
     for (int i = threadIdx.x; i < LAC_Q1_TAB_SIZE * REP; i += blockDim.x) tabr[i] = q1_entry(i / REP, xsh);
@@ -132,26 +112,22 @@ __device__ inline void q1_load_tab_rep(uint32_t *tabr, uint32_t xsh) {
 // thread for 32 copies at 512 threads, before any row load was issued).
 template <int REP, int NTHR>
 __device__ inline void q1_fill_tab_rep(uint32_t *tabr, uint32_t xsh) {
-    if constexpr (!LAC_Q1_FASTFILL) {
-        q1_load_tab_rep<REP>(tabr, xsh);
-    } else {
-        static_assert(REP % 4 == 0, "16-B writes of copies");
-        constexpr int Q = REP / 4, ITEMS = LAC_Q1_TAB_SIZE * Q, IT = (ITEMS + NTHR - 1) / NTHR;
-        uint32_t v[IT];
+    static_assert(REP % 4 == 0, "16-B writes of copies");
+    constexpr int Q = REP / 4, ITEMS = LAC_Q1_TAB_SIZE * Q, IT = (ITEMS + NTHR - 1) / NTHR;
+    uint32_t v[IT];
 #pragma unroll
-        for (int k = 0; k < IT; k++) {
-            const int item = (int)threadIdx.x + k * NTHR;         // entry item / Q, copies 4 (item % Q) ..
-            v[k] = item < ITEMS ? c_q1_tab[kQ1L - item / Q] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < IT; k++) {
-            const int item = (int)threadIdx.x + k * NTHR;
-            uint32_t e = v[k] >> xsh;
-            e = e ? e : 1u;
-            if (item < ITEMS) reinterpret_cast<u32x4 *>(tabr)[item] = u32x4{e, e, e, e};
-        }
-        __syncthreads();
+    for (int k = 0; k < IT; k++) {
+        const int item = (int)threadIdx.x + k * NTHR;         // entry item / Q, copies 4 (item % Q) ..
+        v[k] = item < ITEMS ? c_q1_tab[kQ1L - item / Q] : 0u;
     }
+#pragma unroll
+    for (int k = 0; k < IT; k++) {
+        const int item = (int)threadIdx.x + k * NTHR;
+        uint32_t e = v[k] >> xsh;
+        e = e ? e : 1u;
+        if (item < ITEMS) reinterpret_cast<u32x4 *>(tabr)[item] = u32x4{e, e, e, e};
+    }
+    __syncthreads();
 }
 
 template <int REP = kQ1Rep>
@@ -189,6 +165,31 @@ __device__ inline float wave_max_f32(float v) {
     auto mx = [](uint32_t a, uint32_t b) { return __float_as_uint(fmaxf(__uint_as_float(a), __uint_as_float(b))); };
     return __uint_as_float(wave_reduce(__float_as_uint(v), mx));
 }
+
+// ---------------------------------------------------------------- shared pieces of the
+// three row-statistics kernels (k_q1_stats, k_q1_stats_rl, k_q1_stats_wide)
+//
+// bf16 rows: the maximum over the raw bit patterns as int16 (one v_pk_max_i16 per two
+// logits) is the float maximum whenever the row has a positive, non-NaN maximum
+// (sign-magnitude: positives order as integers and beat every negative).  Other rows (all
+// negative, or a positive NaN) redo it exactly in floats from the same registers.
+// (.x/.y/.z/.w: a bit_cast of v[k] lost 3 of 4 words)
+__device__ inline void max16_vec(s16x2 &pm, const u32x4 &v) {
+    pm = __builtin_elementwise_max(pm, as_s16x2(v.x));
+    pm = __builtin_elementwise_max(pm, as_s16x2(v.y));
+    pm = __builtin_elementwise_max(pm, as_s16x2(v.z));
+    pm = __builtin_elementwise_max(pm, as_s16x2(v.w));
+}
+// the wave's maximum of a lane's packed pair, as a signed int
+__device__ inline int wave_max16(const s16x2 &pm) {
+    const int li = pm.x > pm.y ? (int)pm.x : (int)pm.y;
+    return (int)wave_reduce((uint32_t)li, [](uint32_t a, uint32_t b) {
+        return (uint32_t)((int)a > (int)b ? (int)a : (int)b);
+    });
+}
+// an int16 maximum usable as the row's bf16 maximum: positive (or +0), not NaN
+__device__ inline bool imax_usable(int bi) { return bi >= 0 && bi <= 0x7F80; }
+__device__ inline float imax_to_f32(int bi) { return __uint_as_float((uint32_t)bi << 16); }
 
 // Sum of R per-lane values across the wave, R at once (R a power of two <= 64):
 // a butterfly that halves the live values per step, so lane l ends up holding the
@@ -271,6 +272,19 @@ __device__ inline uint64_t wave_multi_sum32_tail8(uint32_t r) {
     return cross_row_sum64(r);
 }
 constexpr int kHalveOrder[8] = {0, 4, 2, 6, 1, 5, 3, 7};   // butterfly pairs complete early
+// wave_multi_sum32<8>'s butterfly run as the eight sums appear in kHalveOrder: the steps
+// that become possible once vector k (compile-time) has been taken.  At most 3 sums are
+// live instead of 8; sv[0] ends as wave_multi_sum32_tail8's input.
+__device__ inline void halve_stream(uint32_t (&sv)[8], int k) {
+    if (k == 4) sv[0] = halve_pair<0>(sv[0], sv[4]);
+    if (k == 6) { sv[2] = halve_pair<0>(sv[2], sv[6]); sv[0] = halve_pair<1>(sv[0], sv[2]); }
+    if (k == 5) sv[1] = halve_pair<0>(sv[1], sv[5]);
+    if (k == 7) {
+        sv[3] = halve_pair<0>(sv[3], sv[7]);
+        sv[1] = halve_pair<1>(sv[1], sv[3]);
+        sv[0] = halve_pair<2>(sv[0], sv[1]);
+    }
+}
 
 template <int R>
 __device__ inline int q_index(int lane) {                   // lane bit b -> index bit log2(R)-1-b
@@ -280,6 +294,48 @@ __device__ inline int q_index(int lane) {                   // lane bit b -> ind
     return idx;
 }
 
+
+// A row's RowStats from its sums: lo = the entries below the symbol, ps = the symbol's, T = all.
+__device__ inline RowStats q1_row_stats(uint64_t lo, uint64_t ps, uint64_t T) {
+    RowStats st;
+    st.lo = lo;
+    st.hi = lo + ps;
+    st.tot = T;
+    st.minp = 1;                                               // q1 entries are >= 1
+    st.inv_tot = 1.0 / (double)T;
+    st.pad = 0;
+    return st;
+}
+// GROUP (row groups, see k_q1_stats_rl): a segment's partials added into the row's zeroed
+// RowStats (inv_tot 0: the coder divides) with relaxed device-scope atomics; a failed
+// exchange poisons the row's total (>= 2^62: LAC_E_TABLE at the coder); segment 0 sets minp.
+__device__ inline void group_add(uint64_t *p, uint64_t v) {
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+constexpr uint64_t kGroupPoison = 1ull << 62;
+// (ps by reference, read where it is used: k_q1_stats_wide passes its LDS word)
+template <typename P>
+__device__ inline void q1_group_add_stats(RowStats *o, uint64_t lo, const P &ps, uint64_t T, bool ok, bool first) {
+    group_add(&o->tot, T + (ok ? 0 : kGroupPoison));
+    group_add(&o->lo, lo);
+    group_add(&o->hi, lo + ps);
+    if (first) __hip_atomic_store(&o->minp, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One 16-B vector per lane from global memory straight into LDS (LDS-DMA; lds: the wave's
+// 1-KB destination, wave-uniform, through m0, which is saved and restored), nontemporal.
+// As asm: the compiler's own global_load_lds makes every later LDS read wait vmcnt(0) (it
+// cannot tell the slots apart), which serialised the refills.  The asm is invisible to its
+// wait counting, so the callers wait explicitly: vmcnt(0) before pass 1 reads any slot,
+// lgkmcnt(0) before a slot is refilled.
+typedef __attribute__((address_space(3))) void lvoid_t;
+__device__ inline void dma_lds16(const u32x4 *src, uint32_t lds) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(lds)
+                 : "memory");
+}
 
 // Row loads of k_q1_stats, two forms (RowSrc<BUF>):
 //  BUF: a buffer load off one resource per row (wave-uniform row base in SGPRs,
@@ -307,7 +363,7 @@ template <int TB> struct RowSrc<true, TB> {
         : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(row), 0, nv * 16, 0x00020000)), nvec(nv) {}
     __device__ u32x4 operator()(int vi) const {
         const uint32_t v = (uint32_t)(vi < nvec ? vi : nvec - 1);
-        return __builtin_amdgcn_raw_buffer_load_b128(rs, v * 16u, 0, LAC_Q1_NT ? 2 : 0);   // 2 = nt (gfx950)
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, v * 16u, 0, 2);   // 2 = nt (gfx950)
     }
 };
 template <int TB> struct RowSrc<false, TB> {
@@ -315,7 +371,7 @@ template <int TB> struct RowSrc<false, TB> {
     bool ok;
     int nvec;
     __device__ RowSrc(const void *r, bool v, int nv) : row(r), ok(v), nvec(nv) {}
-    __device__ u32x4 operator()(int vi) const { return ok && vi < nvec ? ld16(row, vi, LAC_Q1_NT) : neg_inf16(TB); }
+    __device__ u32x4 operator()(int vi) const { return ok && vi < nvec ? ld16(row, vi, true) : neg_inf16(TB); }
 };
 
 // k_q1_stats: the q1 row statistics.  Persistent blocks of 8 waves (two per CU:
@@ -350,7 +406,7 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
     // that launch aborted its exchanges
     if (gate && __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
     constexpr int N = LogitN<LT>::N, NT = 64 * RW, NR = NWB / RW;
-    constexpr bool IMAX = LAC_Q1_IMAX && sizeof(LT) == 2 && NR == 1 && !MULTI;
+    constexpr bool IMAX = sizeof(LT) == 2 && NR == 1 && !MULTI;
     constexpr bool BUF = R <= 8 && !MULTI;                    // row-load form (RowSrc)
     typedef RowSrc<BUF, sizeof(LT)> Src;
     static_assert(R * N <= 128, "lane sums must fit 32 bits");
@@ -360,7 +416,7 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
     // there -- straight to HBM, with no LDS bins, no second barrier and no writer wave;
     // the maxima's LDS words alternate between rows, so a wave may start the next row
     // while the others still read this one's
-    constexpr bool DIRECT = DEC && !MULTI && RW * R == 64 && !LAC_Q1_DEFER_DEC && LAC_Q1_DEC_DIRECT;
+    constexpr bool DIRECT = DEC && !MULTI && RW * R == 64 && !LAC_Q1_DEFER_DEC;
     __shared__ float smax[2][NWB];
     __shared__ int smaxi[2][NWB];
     __shared__ uint64_t ssum[NWB][2];
@@ -439,31 +495,19 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
         }
         float m;
         if constexpr (IMAX) {
-            // bf16 rows owned by the whole block: the maximum over the raw bit patterns
-            // as int16 (one v_pk_max_i16 per two logits) is the float maximum whenever
-            // the row has a positive, non-NaN maximum (sign-magnitude: positives order
-            // as integers and beat every negative).  Other rows (all negative, or a
-            // positive NaN) redo it exactly in floats from the same registers.
+            // bf16 rows owned by the whole block: the int16 maximum (max16_vec)
             s16x2 pm = {(short)-32768, (short)-32768};
 #pragma unroll
-            for (int j = 0; j < R; j++) {          // (.x/.y/.z/.w: a bit_cast of x[j][k] lost 3 of 4 words)
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].x));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].y));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].z));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].w));
-            }
-            const int li = pm.x > pm.y ? (int)pm.x : (int)pm.y;
-            const int wi = (int)wave_reduce((uint32_t)li, [](uint32_t a, uint32_t b) {
-                return (uint32_t)((int)a > (int)b ? (int)a : (int)b);
-            });
+            for (int j = 0; j < R; j++) max16_vec(pm, x[j]);
+            const int wi = wave_max16(pm);
             if (lane == 0) smaxi[par][w] = wi;
             if (!DEC && gt == 0) sps[g] = 0;
             __syncthreads();
             int bi = smaxi[par][0];
 #pragma unroll
             for (int i = 1; i < NWB; i++) bi = smaxi[par][i] > bi ? smaxi[par][i] : bi;
-            if (bi >= 0 && bi <= 0x7F80) {                    // block-uniform
-                m = __uint_as_float((uint32_t)bi << 16);
+            if (imax_usable(bi)) {                            // block-uniform
+                m = imax_to_f32(bi);
             } else {
 #pragma unroll
                 for (int j = 0; j < R; j++)
@@ -546,16 +590,7 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
             // without it (bf16 c3 decode stats 46-49 vs encode 41 us per step)
             constexpr bool STREAM = DEC && R == 8;
             auto pair_halve = [&](int k) {
-                if constexpr (STREAM) {
-                    if (k == 4) sv[0] = halve_pair<0>(sv[0], sv[4]);
-                    if (k == 6) { sv[2] = halve_pair<0>(sv[2], sv[6]); sv[0] = halve_pair<1>(sv[0], sv[2]); }
-                    if (k == 5) sv[1] = halve_pair<0>(sv[1], sv[5]);
-                    if (k == 7) {
-                        sv[3] = halve_pair<0>(sv[3], sv[7]);
-                        sv[1] = halve_pair<1>(sv[1], sv[3]);
-                        sv[0] = halve_pair<2>(sv[0], sv[1]);
-                    }
-                }
+                if constexpr (STREAM) halve_stream(sv, k);
             };
             // (each halving step runs one vector late: its DPP reads a sum written a whole
             // vector earlier, not the instruction before -- DPP after a VALU write of its
@@ -617,14 +652,7 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
             uint64_t T = 0, L = 0;
 #pragma unroll
             for (int i = 0; i < RW; i++) { T += ssum[g * RW + i][0]; L += ssum[g * RW + i][1]; }
-            RowStats st;
-            st.lo = L;
-            st.hi = L + sps[g];
-            st.tot = T;
-            st.minp = 1;                                       // q1 entries are >= 1
-            st.inv_tot = 1.0 / (double)T;
-            st.pad = 0;
-            out[r] = st;
+            out[r] = q1_row_stats(L, sps[g], T);
         }
     }
     flush_pending();
@@ -647,7 +675,6 @@ __global__ __launch_bounds__(64 * NWB, LAC_Q1_MINW) void k_q1_stats(const LT *__
 // of the last slot, which leaves room for 16 copies (two lanes per copy).
 // Same outputs as k_q1_stats (RowStats, or row max + 64 chunk totals).
 // (kRLRep, kRLLastTrim, kRLTrimMaxVec: lac_select.h)
-typedef __attribute__((address_space(3))) void lvoid_t;
 
 // NT < 1024: 1024 / NT rows per block, NT threads (NT / 64 waves) each, for
 // shorter rows (c3: bf16 V = 32000 with NT = 256, f32 with NT = 512): each wave
@@ -687,13 +714,6 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 constexpr uint32_t kGroupSpinMax = 1u << 17;                 // polls (s_sleep 2 + a device-scope load each): ~0.1 s,
                                                              // far beyond any wait for a resident partner
 
-// DEC: a row's 64 chunk totals are stored after the NEXT row's maximum, not at the
-// row's end, where the store's completion sat in front of the next row's vmcnt(0)
-// (which must wait for this wave's LDS-DMA) and so in front of every wave's barrier
-// (same-box A/B, profiles/r02/q1_defer/: decode stats 0-3 % faster, encode unchanged)
-#ifndef LAC_Q1_DEFER
-#define LAC_Q1_DEFER 1
-#endif
 
 __device__ inline uint64_t group_ld(const uint64_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -756,10 +776,6 @@ __device__ inline uint32_t f32_max_bits(uint32_t a, uint32_t b) {
     return __float_as_uint(fmaxf(__uint_as_float(a), __uint_as_float(b)));
 }
 
-__device__ inline void group_add(uint64_t *p, uint64_t v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-constexpr uint64_t kGroupPoison = 1ull << 62;                 // a failed exchange: the row's total is >= 2^62
 
 template <typename LT, bool DEC, int REP = kRLRep, int LASTN = 1024, int NT = 1024, bool GROUP = false>
 __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ lg, int64_t step_stride,
@@ -770,12 +786,16 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
                                                          uint64_t *__restrict__ xch, int split, int kg, int rpx) {
     constexpr int N = LogitN<LT>::N, R = 8, L = 8, NW = 16, NRB = 1024 / NT, NWR = NT / 64;
     constexpr int SL = (L - 1) * NT + LASTN;                   // slot vectors per row
-    constexpr bool IMAX = LAC_Q1_IMAX && sizeof(LT) == 2;
+    constexpr bool IMAX = sizeof(LT) == 2;
     static_assert(R == kRLRegVec && L == kRLSlots, "q1_slot_cap (lac_select.h) counts these vectors");
     static_assert((R + L) * N <= 128, "lane sums must fit 32 bits");
+    // DEC: a row's 64 chunk totals are stored after the NEXT row's maximum, not at the
+    // row's end, where the store's completion sat in front of the next row's vmcnt(0)
+    // (which must wait for this wave's LDS-DMA) and so in front of every wave's barrier
+    // (same-box A/B, profiles/r02/q1_defer/: decode stats 0-3 % faster, encode unchanged)
     // (not the bf16 8-copy decode forms, which sit at the 128-VGPR cap: two more live
     // registers there add spills)
-    constexpr bool DEFER = LAC_Q1_DEFER && !(sizeof(LT) == 2 && REP == kRLRep);
+    constexpr bool DEFER = !(sizeof(LT) == 2 && REP == kRLRep);
     static_assert(NT == 256 || NT == 512 || NT == 1024, "rows of 4, 8 or 16 waves");
     static_assert(LASTN % 64 == 0 && LASTN <= NT, "the last slot is trimmed by whole waves");
     constexpr bool TRIM = LASTN < NT;
@@ -842,7 +862,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
         group_post_v(v, act);
         return group_poll_v(v, act, op);
     };
-    int64_t pend_r = -1;                                        // DEC, LAC_Q1_DEFER: a row's chunk totals
+    int64_t pend_r = -1;                                        // DEC, DEFER: a row's chunk totals
     uint64_t pend = 0;                                          //   (lane ln: chunk ln) not yet stored
     auto flush_chunks = [&]() {
         if (pend_r < 0) return;
@@ -859,19 +879,12 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
     // maximum, and the sums mask out-of-row vectors)
     auto vidx = [&](int j) { const int vi = j * NT + gti(); return vi < nvec ? vi : nvec - 1; };
     auto ld_reg = [&](const RowSrc<true, sizeof(LT)> &src, int j) { return src(j * NT + gti()); };
-    // LDS-DMA as asm: the compiler's own global_load_lds makes every later LDS read
-    // wait vmcnt(0) (it cannot tell the slots apart), which serialised the refills.
-    // The asm is invisible to its wait counting, so this kernel waits explicitly:
-    // vmcnt(0) before pass 1 reads any slot, lgkmcnt(0) before a slot is refilled.
+    // LDS-DMA (dma_lds16: untracked by the compiler's wait counting, so this kernel waits
+    // explicitly: vmcnt(0) before pass 1 reads any slot, lgkmcnt(0) before a slot is refilled)
     const uint32_t slot_base = (uint32_t)(uintptr_t)(lvoid_t *)&slots[g * SL + wg * 64];   // wave-uniform
     auto ld_lds = [&](const LT *rw, int k) {
         if ((k == L - 1 && noslot) || idle) return;            // wave-uniform
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(rw) + vidx(R + k);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" LAC_Q1_DMA_POLICY "\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(slot_base + (uint32_t)(k * NT * 16))
-                     : "memory");
+        dma_lds16(reinterpret_cast<const u32x4 *>(rw) + vidx(R + k), slot_base + (uint32_t)(k * NT * 16));
     };
     // a row's epilogue, after the barrier that follows its pass 2: its partials (wave
     // sums, the symbol's entry, DEC: group totals) into the outputs
@@ -895,22 +908,8 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
             uint64_t T = 0, Ls = 0;
 #pragma unroll
             for (int i = 0; i < NWR; i++) { T += ssum[g * NWR + i][0]; Ls += ssum[g * NWR + i][1]; }
-            if constexpr (GROUP) {                              // the segments' partials add up
-                RowStats *o = out + er;                        // (zeroed; inv_tot 0: the coder divides)
-                group_add(&o->tot, T + (eok ? 0 : kGroupPoison));
-                group_add(&o->lo, Ls);
-                group_add(&o->hi, Ls + ps);
-                if (hh == 0) __hip_atomic_store(&o->minp, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                RowStats st;
-                st.lo = Ls;
-                st.hi = Ls + ps;
-                st.tot = T;
-                st.minp = 1;
-                st.inv_tot = 1.0 / (double)T;
-                st.pad = 0;
-                out[er] = st;
-            }
+            if constexpr (GROUP) q1_group_add_stats(out + er, Ls, ps, T, eok, hh == 0);   // the segments' partials add up
+            else out[er] = q1_row_stats(Ls, ps, T);
         }
     };
     u32x4 x[R];
@@ -945,20 +944,11 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
         pok = true;
         if constexpr (IMAX) {
             s16x2 pm = {(short)-32768, (short)-32768};
-            auto pmax = [&](const u32x4 &v) {
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.x));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.y));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.z));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.w));
-            };
 #pragma unroll
-            for (int j = 0; j < R; j++) pmax(x[j]);
+            for (int j = 0; j < R; j++) max16_vec(pm, x[j]);
 #pragma unroll
-            for (int k = 0; k < L; k++) pmax(slot(k));
-            const int li = pm.x > pm.y ? (int)pm.x : (int)pm.y;
-            const int wi = (int)wave_reduce((uint32_t)li, [](uint32_t a, uint32_t b) {
-                return (uint32_t)((int)a > (int)b ? (int)a : (int)b);
-            });
+            for (int k = 0; k < L; k++) max16_vec(pm, slot(k));
+            const int wi = wave_max16(pm);
             if (lane == 0) smaxi[w] = wi;
             if (!DEC && gti() == 0) sps[g] = 0;
             __syncthreads();
@@ -969,7 +959,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
                 int bm = smaxi[gg * NWR];
 #pragma unroll
                 for (int i = 1; i < NWR; i++) bm = smaxi[gg * NWR + i] > bm ? smaxi[gg * NWR + i] : bm;
-                all_ok = all_ok && bm >= 0 && bm <= 0x7F80;
+                all_ok = all_ok && imax_usable(bm);
                 bi = gg == g ? bm : bi;
             }
             bool my_ok = true;                                 // GROUP: this row's combined int max usable
@@ -977,14 +967,14 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
                 bi = (int)group_combine((uint32_t)bi, valid, [](uint32_t a, uint32_t b) {
                     return (int)a > (int)b ? a : b;
                 });
-                my_ok = !valid || (bi >= 0 && bi <= 0x7F80);
+                my_ok = !valid || imax_usable(bi);
                 all_ok = true;                                 // (block-uniform: every exchanging row's combined max)
 #pragma unroll
                 for (int gg = 0; gg < NRB; gg++)
-                    all_ok = all_ok && (!sxact[gg] || ((int)sxv[gg] >= 0 && (int)sxv[gg] <= 0x7F80));
+                    all_ok = all_ok && (!sxact[gg] || imax_usable((int)sxv[gg]));
             }
-            if (all_ok) {                                      // (see k_q1_stats)
-                m = __uint_as_float((uint32_t)bi << 16);
+            if (all_ok) {                                      // (see max16_vec)
+                m = imax_to_f32(bi);
             } else {
                 float mx = -INFINITY;
 #pragma unroll
@@ -1006,7 +996,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
                 if constexpr (GROUP) {                          // only the rows whose int max failed exchange again
                     const float mf = __uint_as_float(group_combine(
                         __float_as_uint(m), valid && !my_ok, [](uint32_t a, uint32_t b) { return f32_max_bits(a, b); }));
-                    m = my_ok ? __uint_as_float((uint32_t)bi << 16) : mf;
+                    m = my_ok ? imax_to_f32(bi) : mf;
                 }
             }
         } else {
@@ -1033,7 +1023,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
                                                   [](uint32_t a, uint32_t b) { return f32_max_bits(a, b); }));
         }
         if (DEC && valid && gti() == 0 && hh == 0) mrow[r] = m;   // now: m is not held over pass 2
-        if constexpr (DEC) flush_chunks();                    // the previous row's (LAC_Q1_DEFER)
+        if constexpr (DEC) flush_chunks();                    // the previous row's (DEFER)
         const bool fast = q1_fast_row(m);
         const float c = q1_c(m);
         int sfull = -1, sr = 0;
@@ -1091,15 +1081,7 @@ __global__ __launch_bounds__(1024, 4) void k_q1_stats_rl(const LT *__restrict__ 
             if (ln < 8) gtot[g * NWR * (R + L) + wg + NWR * (j0 + q_index<8>(ln))] = gsum;   // [grp*64, +64)
         };
         auto pair_halve = [&](int k) {                         // k: the vector just taken (compile-time)
-            if (!DEC) return;
-            if (k == 4) sv[0] = halve_pair<0>(sv[0], sv[4]);
-            if (k == 6) { sv[2] = halve_pair<0>(sv[2], sv[6]); sv[0] = halve_pair<1>(sv[0], sv[2]); }
-            if (k == 5) sv[1] = halve_pair<0>(sv[1], sv[5]);
-            if (k == 7) {
-                sv[3] = halve_pair<0>(sv[3], sv[7]);
-                sv[1] = halve_pair<1>(sv[1], sv[3]);
-                sv[0] = halve_pair<2>(sv[0], sv[1]);
-            }
+            if (DEC) halve_stream(sv, k);
         };
         auto pass2 = [&](bool fs) {
 #pragma unroll
@@ -1165,7 +1147,7 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
                                                           uint64_t *__restrict__ chunks, float *__restrict__ mrow,
                                                           uint64_t *__restrict__ xch, int split, int kg, int rpx) {
     constexpr int N = LogitN<LT>::N, NT = kQ1WideThreads, NW = NT / 64;
-    constexpr bool IMAX = LAC_Q1_IMAX && sizeof(LT) == 2;
+    constexpr bool IMAX = sizeof(LT) == 2;
     static_assert(R % 8 == 0, "group totals in batches of 8 vectors");
     __shared__ uint32_t tabr[LAC_Q1_TAB_SIZE * kQ1Rep];
     __shared__ float smax[NW];
@@ -1218,21 +1200,16 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
         // soffset materialised next to its load (asm): 40 hoisted constants spilled SGPRs
         uint32_t so;
         asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "i"(j * NT * 16));
-        return __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)tid * 16u, so, LAC_Q1_NT ? 2 : 0);
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)tid * 16u, so, 2);
     };
-    // LDS-DMA as asm (see k_q1_stats_rl: untracked by the compiler's wait counting, so
-    // pass 1 waits vmcnt(0) itself and a slot is refilled after lgkmcnt(0)); lanes past
-    // the row load its last vector (masked when read)
+    // LDS-DMA (dma_lds16: untracked by the compiler's wait counting, so pass 1 waits
+    // vmcnt(0) itself and a slot is refilled after lgkmcnt(0)); lanes past the row load its
+    // last vector (masked when read)
     const uint32_t slot_base = (uint32_t)(uintptr_t)(lvoid_t *)&slots[w * 64];   // wave-uniform
     auto ld_slot = [&](const LT *rw, int k, int ti_, int nv_) {
         // (ti_, nv_ opaque per row: 11 hoisted clamped offsets spilled the bf16 decode form)
         const int vi = ti_ + NT * (R + k);
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(rw) + (vi < nv_ ? vi : nv_ - 1);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" LAC_Q1_DMA_POLICY "\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(src), "s"(slot_base + (uint32_t)(k * NT * 16))
-                     : "memory");
+        dma_lds16(reinterpret_cast<const u32x4 *>(rw) + (vi < nv_ ? vi : nv_ - 1), slot_base + (uint32_t)(k * NT * 16));
     };
     u32x4 x[R];
     {                                                          // the first row, in flight during the table fill
@@ -1279,27 +1256,13 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
             return ti + NT * (R + kk) < nv ? v : neg_inf16(sizeof(LT));
         };
         float m;
-        if constexpr (IMAX) {                                  // (see k_q1_stats)
+        if constexpr (IMAX) {                                  // (see max16_vec)
             s16x2 pm = {(short)-32768, (short)-32768};
 #pragma unroll
-            for (int j = 0; j < R; j++) {
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].x));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].y));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].z));
-                pm = __builtin_elementwise_max(pm, as_s16x2(x[j].w));
-            }
+            for (int j = 0; j < R; j++) max16_vec(pm, x[j]);
 #pragma unroll
-            for (int kk = 0; kk < L; kk++) {
-                const u32x4 v = slot(kk);
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.x));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.y));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.z));
-                pm = __builtin_elementwise_max(pm, as_s16x2(v.w));
-            }
-            const int li = pm.x > pm.y ? (int)pm.x : (int)pm.y;
-            const int wi = (int)wave_reduce((uint32_t)li, [](uint32_t a, uint32_t b) {
-                return (uint32_t)((int)a > (int)b ? (int)a : (int)b);
-            });
+            for (int kk = 0; kk < L; kk++) max16_vec(pm, slot(kk));
+            const int wi = wave_max16(pm);
             if (lane == 0) smaxi[w] = wi;
             if (!DEC && tid == 0) sps = 0;
             __syncthreads();
@@ -1308,8 +1271,8 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
             for (int i = 1; i < NW; i++) bi = smaxi[i] > bi ? smaxi[i] : bi;
             if constexpr (GROUP)                               // the int max of all segments
                 bi = (int)group_combine((uint32_t)bi, [](uint32_t a, uint32_t b) { return (int)a > (int)b ? a : b; });
-            if (bi >= 0 && bi <= 0x7F80) {                    // block-uniform (GROUP: the same in every segment)
-                m = __uint_as_float((uint32_t)bi << 16);
+            if (imax_usable(bi)) {                            // block-uniform (GROUP: the same in every segment)
+                m = imax_to_f32(bi);
             } else {
                 float mx = -INFINITY;
 #pragma unroll
@@ -1402,6 +1365,21 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
         // Batches wholly past the row (NT j0 >= nv, uniform) skip their sums; their loads
         // are still issued (past the row they touch no memory) so that the registers
         // never meet from two paths.
+        // DEC: a batch's 8 lane sums (vectors j0 .. j0 + 7, registers or slots) as its 8 group
+        // totals into the chunk bins.  (The encode form's sums stay written out at both
+        // places on purpose: through a shared lambda the two L = 11 encode instances change.)
+        auto bin_batch = [&](int j0, uint32_t (&sv)[8]) {
+            // group (w + 8 j) = vectors [64 (w + 8 j), +64): wave w's vector j
+            uint64_t gsum = wave_multi_sum32<8>(sv);            // lane l < 8: vector j0 + q_index<8>(l)
+            if (lane < 8) {
+                // (the lane index fresh here: hoisted, the 7 batches' bin addresses spilled and
+                //  their reloads' vmcnt(0) drained the rolling prefetch)
+                const int grp = w + NW * (j0 + q_index<8>(lane_fresh())), past = (grp + 1) * 64 - nv;
+                if (past > 0 && past < 64) gsum -= (uint64_t)past * N * tab0;   // the row's last group
+                // (GROUP: segment group grp is the row's group vofs / 64 + grp; split is a multiple of 64)
+                if (grp * 64 < nv) atomicAdd(&bins[chunk_of(vofs / 64 + grp)], (unsigned long long)gsum);
+            }
+        };
         auto batch = [&](int j0) {
             uint32_t sv[8];
             const bool live = NT * j0 < nv;
@@ -1420,16 +1398,7 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
             for (int u = 0; u < 8; u++) x[j0 + u] = load_vec(rsn, j0 + u);
             if (!live) return;
             if constexpr (DEC) {
-                // group (w + 8 j) = vectors [64 (w + 8 j), +64): wave w's vector j
-                uint64_t gsum = wave_multi_sum32<8>(sv);        // lane l < 8: vector j0 + q_index<8>(l)
-                if (lane < 8) {
-                    // (the lane index fresh here: hoisted, the 7 batches' bin addresses spilled and
-                    //  their reloads' vmcnt(0) drained the rolling prefetch)
-                    const int grp = w + NW * (j0 + q_index<8>(lane_fresh())), past = (grp + 1) * 64 - nv;
-                    if (past > 0 && past < 64) gsum -= (uint64_t)past * N * tab0;   // the row's last group
-                    // (GROUP: segment group grp is the row's group vofs / 64 + grp; split is a multiple of 64)
-                    if (grp * 64 < nv) atomicAdd(&bins[chunk_of(vofs / 64 + grp)], (unsigned long long)gsum);
-                }
+                bin_batch(j0, sv);
             } else {
                 uint32_t bt = 0, bl = 0;
 #pragma unroll
@@ -1468,12 +1437,7 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
                 __builtin_amdgcn_sched_barrier(0);
                 const int j0 = R + k0;
                 if constexpr (DEC) {
-                    uint64_t gsum = wave_multi_sum32<8>(sv);
-                    if (lane < 8) {
-                        const int grp = w + NW * (j0 + q_index<8>(lane_fresh())), past = (grp + 1) * 64 - nv;
-                        if (past > 0 && past < 64) gsum -= (uint64_t)past * N * tab0;
-                        if (grp * 64 < nv) atomicAdd(&bins[chunk_of(vofs / 64 + grp)], (unsigned long long)gsum);
-                    }
+                    bin_batch(j0, sv);
                 } else {
                     uint32_t bt = 0, bl = 0;
 #pragma unroll
@@ -1511,22 +1475,8 @@ __global__ __launch_bounds__(512, 2) void k_q1_stats_wide(const LT *__restrict__
             // vectors of the live batches (L > 0: rows past the registers, every batch live)
             const int nsum = L > 0 ? NT * (R + L) : 8 * NT * ((nv + 8 * NT - 1) / (8 * NT));
             T -= (uint64_t)(nsum - nv) * N * tab0;             // those past the row
-            if constexpr (GROUP) {                              // the segments' partials add up
-                RowStats *o = out + r;                         // (zeroed; inv_tot 0: the coder divides)
-                group_add(&o->tot, T + (pok ? 0 : kGroupPoison));
-                group_add(&o->lo, Ls);
-                group_add(&o->hi, Ls + sps);
-                if (hh == 0) __hip_atomic_store(&o->minp, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                RowStats st;
-                st.lo = Ls;
-                st.hi = Ls + sps;
-                st.tot = T;
-                st.minp = 1;
-                st.inv_tot = 1.0 / (double)T;
-                st.pad = 0;
-                out[r] = st;
-            }
+            if constexpr (GROUP) q1_group_add_stats(out + r, Ls, sps, T, pok, hh == 0);   // the segments' partials add up
+            else out[r] = q1_row_stats(Ls, sps, T);
         }
     }
     if constexpr (L > 0) {
@@ -1709,8 +1659,7 @@ __global__ LAC_DEC_BOUNDS void k_q1_decode(const LT *__restrict__ lg, int64_t st
                     const bool det = vh < w && thi < hi_c;
                     if (st.det && det) st.ndet++;
                     else st.det = 0;
-                    err = LAC_Q1D_NB ? decode_advance_nb(st, a, bb, win, mynbits, prec)
-                                     : decode_advance<true>(st, a, bb, win, mynbits, prec);
+                    err = decode_advance_nb(st, a, bb, win, mynbits, prec);
                 }
             }
         }
@@ -1795,7 +1744,7 @@ __device__ inline void q1_step_row(const LT *row, int nvec, uint32_t xsh, StepSh
 #pragma unroll
     for (int j = 0; j < R; j++) {
         const int vi = v0 + 64 * j;
-        x[j] = ld16(row, vi < nvec ? vi : nvec - 1, LAC_Q1_NT);
+        x[j] = ld16(row, vi < nvec ? vi : nvec - 1, true);
     }
     for (int i = threadIdx.x; i < LAC_Q1_TAB_SIZE * kStepRep; i += blockDim.x) sh.tab[i] = q1_entry(i / kStepRep, xsh);
     float mx = -INFINITY;
@@ -1966,8 +1915,7 @@ __global__ __launch_bounds__(kQ1StepMaxThreads) void k_q1_step_dec(const LT *__r
             const bool det = vh < wd && thi < hi_c;
             if (st.det && det) st.ndet++;
             else st.det = 0;
-            err = LAC_Q1D_NB ? decode_advance_nb(st, a, bb, win, mynbits, prec)
-                             : decode_advance<true>(st, a, bb, win, mynbits, prec);
+            err = decode_advance_nb(st, a, bb, win, mynbits, prec);
         }
         if (err) {
             st.err = err;

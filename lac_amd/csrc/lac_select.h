@@ -300,9 +300,6 @@ inline Q1StepPlan q1_step_plan(int cus, int64_t V, int type_bytes, int64_t strea
 #ifndef LAC_LEAN
 #define LAC_LEAN 1         // few-stream decode: k_decode_lean ahead of k_decode_seq (probe builds set 0)
 #endif
-#ifndef LAC_LEAN_HELP
-#define LAC_LEAN_HELP 1     // k_decode_lean: L2-prefetching helper workgroups for <= 16 streams
-#endif
 // The lean step's chunks: up to 64 * LeanCW<E> of them, LeanCW bounds per lane -- u64 rows
 // two (V = 32000: 125 chunks of 2 iterations, two 16-B loads per lane and step instead of
 // four), u32 rows one (dec_chunk_layout's layout).
@@ -417,6 +414,6 @@ inline DecodePlan decode_plan(const DecodeKnobs &k, int64_t B, int64_t V, int pm
     }
     // prefetching helper workgroups for the fewest streams (kLeanHelpers per stream, dealt
     // to the stream's XCD); a static model's rows stay in L2 without them
-    p.help = p.lean && !p.static_rows && LAC_LEAN_HELP && B <= kLeanHelpMaxStreams;
+    p.help = p.lean && !p.static_rows && B <= kLeanHelpMaxStreams;
     return p;
 }

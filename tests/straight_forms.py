@@ -1,5 +1,5 @@
 """Which straight 64-step form of the split-path encoder (lac_amd/csrc/lac_encode.hip
-k_encode, LAC_ENC_STRAIGHT) each block of a fixture takes when coded untraced -- a
+k_encode's straight blocks) each block of a fixture takes when coded untraced -- a
 restatement of the kernel's block test for the tests, so they can show that reference-run
 fixtures reach every form.
 
