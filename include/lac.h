@@ -508,6 +508,52 @@ int lac_decode_step(lac_ctx *ctx, const void *pmf_dev, int64_t stream_stride,
 int lac_decode_steps(lac_ctx *ctx, const void *pmf_dev, int64_t step_stride, int64_t stream_stride,
                      int64_t steps, int32_t *sym_out_dev, void *stream);
 
+/* ---- finite-state models (the reference's NFA predictor, arith_code.py:423-434) ----------
+ * A model has K states over the context's V symbols: integer tables pmf[K][V] in the context's
+ * pmf_bits and transitions next[K][V] (int32).  Stream b starts in state q_0 = its current state
+ * (lac_fsm_set_states); step t codes sym_t with row pmf[q_t] exactly as lac_encode /
+ * lac_decode_steps code that row -- ceil mapping, fudged rows included -- and then
+ * q_{t+1} = next[q_t][sym_t] (NFA.calc_dist / NFA.accept, :427-432).  In the explicit-states form
+ * the caller passes states[steps][streams] and q_t = states[t][b]; next is not consulted and the
+ * context's current states do not move.  Per stream everything -- output bytes and nbits,
+ * registers, decoded symbols, lac_stream_status codes and err_step, what a failed stream
+ * freezes -- is what the pmf path gives on the gathered tables pmf[q_t], so either path decodes
+ * the other's streams.  One kernel launch per call whatever the steps; the launches report under
+ * lac_profile_read's slots 1 (encode) and 3 (decode_step).
+ *
+ * lac_fsm_load  (NFA.__init__, :424-426) copies the model into a prepared device form the context
+ *   owns (per state row: the per-entry CDF, T, ceil(T / minp), 1 / T; lac_amd/csrc/lac_fsm.h); the
+ *   caller's buffers are free when it returns (it synchronises `stream`), lac_close frees the
+ *   prepared form, and every stream's current state becomes 0.  pmf_dev: [states][V] contiguous,
+ *   any alignment; next_dev: [states][V] int32 or NULL (explicit-states form only).
+ *   Limits: V <= 65536 and states * V <= 2^24 entries (an order-2 byte model fits); beyond
+ *   either, LAC_E_ARG.  A next entry outside [0, states): LAC_E_TABLE, the model in place stays.
+ *   A load replaces the model only between jobs: LAC_E_STATE after an lac_encode / lac_fsm_encode
+ *   that is not finished, or after an lac_fsm_decode with no lac_decode_open* since.  A bad row
+ *   (empty, total >= 2^64) is no load error: it raises the pmf path's sticky LAC_E_TABLE for the
+ *   stream whose step reaches it.
+ * lac_fsm_set_states / lac_fsm_get_states  (NFA.s, :426) the current state of every stream (int32
+ *   [streams], device memory, copied on `stream`; NULL sets all to 0).  A state outside
+ *   [0, states) is LAC_E_TABLE for its stream at the step that uses it, in both forms.
+ * lac_fsm_encode  (A_to_bin.step with NFA.calc_dist + accept, :187-192, :427-432) continues the
+ *   open encode like lac_encode: sym_dev int32 [steps][streams], states_dev int32
+ *   [steps][streams] or NULL, trace_dev as lac_encode's (per (t, b) the symbol's digits {E, k}) or NULL.  lac_encode_reset, _drain, _rebase, _finish, the checkpoint calls and
+ *   lac_set_output work around it unchanged.  A failed stream keeps the state of its failing step.
+ * lac_fsm_decode  (A_from_bin.step, :264-299) after any lac_decode_open*: sym_out_dev int32
+ *   [steps][streams] (-1 after an error); it reads the opened buffer like every decode path, so
+ *   lac_decode_refill works between calls, and honours LAC_OPT_DECODE_STOP (LAC_E_UNDETERMINED,
+ *   registers and state unchanged) and lac_decode_determined.
+ * Both coding calls honour lac_set_stream_lengths.  Refused before anything is launched:
+ * LAC_E_STATE with no model loaded, under LAC_MAP_FLOOR (the reference's NFA is a CDFPredictor)
+ * or in the wrong mode (lac_encode's / lac_decode_steps' rule); LAC_E_ARG for states_dev NULL on a
+ * model loaded without next. */
+int lac_fsm_load(lac_ctx *ctx, const void *pmf_dev, const int32_t *next_dev, int64_t states, void *stream);
+int lac_fsm_set_states(lac_ctx *ctx, const int32_t *state_dev, void *stream);
+int lac_fsm_get_states(lac_ctx *ctx, int32_t *state_dev_out, void *stream);
+int lac_fsm_encode(lac_ctx *ctx, const int32_t *sym_dev, const int32_t *states_dev, int64_t steps,
+                   uint64_t *trace_dev, void *stream);
+int lac_fsm_decode(lac_ctx *ctx, const int32_t *states_dev, int64_t steps, int32_t *sym_out_dev, void *stream);
+
 /* ---- logits path --------------------------------
  * Tables are computed in-kernel from raw logits with the integer-exact "q1"
  * quantiser instead of being read from a pmf in HBM: for each row

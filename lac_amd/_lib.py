@@ -76,6 +76,11 @@ PROTOTYPES = [
     ("lac_decode_step", _i, [_vp, _vp, _i64, _vp, _vp]),
     ("lac_decode_steps", _i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     ("lac_decode_determined", _i, [_vp, _vp, _vp]),
+    ("lac_fsm_load", _i, [_vp, _vp, _vp, _i64, _vp]),
+    ("lac_fsm_set_states", _i, [_vp, _vp, _vp]),
+    ("lac_fsm_get_states", _i, [_vp, _vp, _vp]),
+    ("lac_fsm_encode", _i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    ("lac_fsm_decode", _i, [_vp, _vp, _i64, _vp, _vp]),
     ("lac_decode_get_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_set_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_tail_begin", _i, [_vp, _vp]),

@@ -573,6 +573,111 @@ class BatchCoder:
                                         C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    # ------------------------------------------------------------ finite-state models
+    def load_fsm(self, tables, next=None):
+        """Load a finite-state model (include/lac.h lac_fsm_load; the reference's
+        NFA(state, transitions), arith_code.py:423-434): ``tables`` [K, vocab] integer pmf rows,
+        one per state (a numpy array, or a device tensor in the coder's entry type), ``next``
+        [K, vocab] int32 transitions or None for a model coded with explicit states only.  The
+        model is copied into a prepared form the coder owns -- the arguments are free afterwards
+        -- and every stream's state becomes 0.  Only between jobs.  K * vocab <= 2^24 and
+        vocab <= 65536; a transition outside [0, K) raises LacError(LAC_E_TABLE)."""
+        torch = _torch()
+        if isinstance(tables, torch.Tensor):
+            self._check_pmf(tables)
+            tab = tables.contiguous()
+        else:
+            a = np.asarray(tables)
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"tables must be integers, got {a.dtype}")
+            u, i = (np.uint32, np.int32) if self.pmf_bits == 32 else (np.uint64, np.int64)
+            tab = torch.from_numpy(np.ascontiguousarray(a.astype(u)).view(i)).to(self.device)
+        if tab.dim() != 2 or tab.shape[1] != self.vocab:
+            raise ValueError(f"tables must be [states, {self.vocab}], got {tuple(tab.shape)}")
+        nxt = None
+        if next is not None:
+            nxt = next if isinstance(next, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(next), dtype=np.int32))
+            if nxt.dtype != torch.int32 or tuple(nxt.shape) != tuple(tab.shape):
+                raise ValueError(f"next must be int32 {tuple(tab.shape)}")
+            nxt = nxt.to(self.device).contiguous()
+        check(self.lib.lac_fsm_load(self.ctx, C.c_void_p(tab.data_ptr()),
+                                    None if nxt is None else C.c_void_p(nxt.data_ptr()), tab.shape[0], self._stream))
+        self.fsm_states_count = int(tab.shape[0])
+
+    def _fsm_state_rows(self, states, steps):
+        """-> a contiguous int32 device tensor [steps, streams] (kept referenced), or None."""
+        if states is None:
+            return None
+        torch = _torch()
+        if not isinstance(states, torch.Tensor):
+            states = torch.from_numpy(np.ascontiguousarray(np.asarray(states), dtype=np.int32))
+        if states.dtype != torch.int32 or tuple(states.shape) != (steps, self.streams):
+            raise ValueError(f"states must be int32 [{steps}, {self.streams}]")
+        return states.to(self.device).contiguous()
+
+    def set_fsm_states(self, states=None):
+        """The current state of every stream (lac_fsm_set_states): ``streams`` integers, or
+        None for state 0 everywhere.  Copied; kept in the coder across calls."""
+        if states is None:
+            check(self.lib.lac_fsm_set_states(self.ctx, None, self._stream))
+            return
+        torch = _torch()
+        arr = states.detach().cpu().numpy() if isinstance(states, torch.Tensor) else np.asarray(states)
+        dev = self._fsm_state_rows(arr.reshape(1, -1), 1)
+        check(self.lib.lac_fsm_set_states(self.ctx, C.c_void_p(dev.data_ptr()), self._stream))
+        self._fsm_keep = dev
+
+    def fsm_states(self):
+        """Every stream's current state (int32 numpy [streams]); synchronises."""
+        torch = _torch()
+        out = torch.empty((self.streams,), dtype=torch.int32, device=self.device)
+        check(self.lib.lac_fsm_get_states(self.ctx, C.c_void_p(out.data_ptr()), self._stream))
+        return out.cpu().numpy()
+
+    def encode_fsm(self, sym, states=None, trace=None):
+        """Continue every stream by ``sym`` [steps, streams] (int32 device tensor) under the
+        loaded model, in one launch: step t codes with the row of the stream's state and moves
+        it by ``next`` -- or, with ``states`` [steps, streams], with the row of states[t, b].
+        Bit for bit :meth:`encode` on the gathered rows; ``trace`` as there."""
+        torch = _torch()
+        if sym.dtype != torch.int32 or sym.device != self.device:
+            raise TypeError("sym must be an int32 tensor on the coder's device")
+        sym = sym.contiguous()
+        steps = sym.shape[0] if sym.dim() == 2 else 1
+        if sym.numel() != steps * self.streams:
+            raise ValueError(f"sym must be [steps, {self.streams}]")
+        st = self._fsm_state_rows(states, steps)
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int64 or trace.numel() != steps * self.streams * 2 or not trace.is_contiguous():
+                raise ValueError("trace must be a contiguous int64 tensor [steps, streams, 2]")
+            tp = C.c_void_p(trace.data_ptr())
+        self._keep = (sym, st)
+        check(self.lib.lac_fsm_encode(self.ctx, C.c_void_p(sym.data_ptr()),
+                                      None if st is None else C.c_void_p(st.data_ptr()), steps, tp, self._stream))
+
+    def encode_fsm_job(self, sym, state0=None, states=None):
+        """reset + set_fsm_states(state0) + encode_fsm + finish."""
+        self.reset()
+        self.set_fsm_states(state0)
+        self.encode_fsm(sym, states)
+        self.finish()
+
+    def decode_fsm(self, steps, states=None, out=None):
+        """Decode ``steps`` symbols per stream under the loaded model in one launch (after any
+        decode_open*); ``states`` as in :meth:`encode_fsm`.  -> int32 [steps, streams]."""
+        torch = _torch()
+        steps = int(steps)
+        if out is None:
+            out = torch.empty((steps, self.streams), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out(out, steps)
+        st = self._fsm_state_rows(states, steps)
+        self._keep = (st,)
+        check(self.lib.lac_fsm_decode(self.ctx, None if st is None else C.c_void_p(st.data_ptr()), steps,
+                                      C.c_void_p(out.data_ptr()), self._stream))
+        return out
 
     # ------------------------------------------------------------ logits path
     def _logits_args(self, logits, steps=None):

@@ -6,6 +6,7 @@ Drop-in counterparts of /root/reference/arith_code.py:
     Predictor               :64-74   (uniform n-ary; floor mapping)
     CDFPredictor            :76-110  (CDF table; ceil mapping; fudged_dist)
     ProbPredictor           :111-135 (prob / calc_dist / cached dist)
+    NFA                     :423-434 (finite-state model: one CDF and one transition row per state)
     AC                      :144-155 (.to_bin / .from_bin make fresh coders)
     A_to_bin                :156-246 (step, run, bits, encode, flush, __call__)
     A_from_bin              :248-334 (step, run, decode)
@@ -143,6 +144,30 @@ class ProbPredictor(CDFPredictor):
         return self
 
 
+class NFA(ProbPredictor):
+    """Finite-state predictor (arith_code.py:423-434): ``transitions[q]`` is
+    ``(cdf, next_by_symbol)``; ``calc_dist`` returns the current state's CDF and
+    ``accept`` moves the state.  (``dcache`` is initialised here, which the
+    reference's ``__init__`` omits.)  A_to_bin / A_from_bin code such a predictor
+    in one launch through liblac's finite-state kernels (``_fsm_model``)."""
+
+    def __init__(self, state, transitions):
+        self.t = transitions
+        self.s = state
+        self.dcache = None
+
+    def calc_dist(self):
+        self.dcache = self.t[self.s][0]
+        return self.dcache
+
+    def accept(self, symbol):
+        self.s = self.t[self.s][1][symbol]
+        return super().accept(symbol)
+
+    def copy(self):
+        return NFA(self.s, self.t)
+
+
 ternary = Predictor(3)
 
 
@@ -272,6 +297,61 @@ def _declared_minp(predictor):
     return getattr(predictor, "minp", None)
 
 
+def _fsm_model(predictor):
+    """(tables uint64 [K, V], next int32 [K, V]) when ``predictor`` is the reference's NFA
+    (arith_code.py:423-434) as liblac's finite-state kernels can code it, else None: its
+    ``calc_dist`` and ``accept`` resolve to NFA's own (in the reference's module or this one --
+    a subclass overriding either keeps the per-token path), its mapping is CDFPredictor's, it
+    declares no ``minp`` of its own, and its ``transitions`` are K rows of an integer CDF of one
+    length V (values within 64 bits) with V transitions into [0, K) each."""
+    for m in ("calc_dist", "accept"):
+        if _impl(predictor, m) not in ((f"NFA.{m}", mod) for mod in _REF_MODULES):
+            return None
+    if not _is_table(predictor) or _declared_minp(predictor) is not None:
+        return None
+    t = getattr(predictor, "t", None)
+    try:
+        K = len(t)
+        V = len(t[0][0]) if K else 0
+        if not K or not V or V > 65536 or K * V > 1 << 24 or not 0 <= int(predictor.s) < K:
+            return None
+        tables = np.empty((K, V), dtype=np.uint64)
+        nxt = np.empty((K, V), dtype=np.int64)
+        for q in range(K):
+            cdf, nq = t[q][0], t[q][1]
+            a = _cdf_array(cdf)
+            if a is None or len(a) != V or len(nq) != V:
+                return None
+            if a.dtype.kind == "i" and bool((a < 0).any()):
+                return None
+            a = a.astype(np.uint64, copy=False)
+            if V > 1 and bool((a[1:] < a[:-1]).any()):
+                return None
+            tables[q, 0] = a[0]
+            np.subtract(a[1:], a[:-1], out=tables[q, 1:])
+            nxt[q] = np.fromiter((int(x) for x in nq), dtype=np.int64, count=V)
+    except (TypeError, ValueError, OverflowError, IndexError, KeyError):
+        return None
+    if bool(((nxt < 0) | (nxt >= K)).any()):
+        return None
+    return tables, nxt.astype(np.int32)
+
+
+def _fsm_model_still(predictor):
+    """The cheap part of _fsm_model's test, for a predictor whose tables were converted before."""
+    return all(_impl(predictor, m) in ((f"NFA.{m}", mod) for mod in _REF_MODULES) for m in ("calc_dist", "accept")) \
+        and isinstance(getattr(predictor, "s", None), (int, np.integer)) and 0 <= int(predictor.s) < len(predictor.t)
+
+
+class _FsmRows:
+    """Stands for the rows of a finite-state job in A_to_bin._encode_rows: the device gathers
+    them itself (BatchCoder.encode_fsm), one 'static row' of V entries as far as chunking goes."""
+    ndim = 1
+
+    def __init__(self, V):
+        self.shape = (V,)
+
+
 def fudge_decisions_agree(T, minp, min_pos, prec):
     """Whether fudged_dist's test ``T > w*minp`` (arith_code.py:84) with the
     predictor's ``minp`` and with the table's smallest positive entry
@@ -396,6 +476,30 @@ class A_to_bin:
         self._tab = None
         self._plane_bits = 0          # output bits held in the device planes since the last reset
         self._nsym = 0                # symbols coded since the last reset
+        self._fsm = None              # (transitions object, _fsm_model of it): converted once
+        self._fsm_on = None           # the BatchCoder that holds the model
+
+    def _fsm_tables(self):
+        """The predictor as a finite-state model (``_fsm_model``), or None."""
+        t = getattr(self.predictor, "t", None)
+        if self._fsm is None or self._fsm[0] is not t:
+            self._fsm = (t, _fsm_model(self.predictor))
+        return self._fsm[1] if _fsm_model_still(self.predictor) else None
+
+    def _fsm_begin(self, model, steps):
+        """Coder, model and start state on the device; False when the model cannot be loaded
+        now (the coder is in mid-stream and holds none: the per-token path goes on)."""
+        V = model[0].shape[1]
+        if self._coder is not None and self._V != V and not self._fresh():
+            return False
+        if self._coder is not None and self._fsm_on is not self._coder and not self._fresh():
+            return False
+        self._ensure(V, steps)
+        if self._fsm_on is not self._coder:
+            self._coder.load_fsm(model[0], model[1])
+            self._fsm_on = self._coder
+        self._coder.set_fsm_states([int(self.predictor.s)])
+        return True
 
     def _tables(self, begin=True):
         t = self._tab
@@ -476,12 +580,15 @@ class A_to_bin:
         import torch
         steps = len(syms)
         dev = self._coder.device
-        if rows.ndim == 1:
-            pmf = self._tab.row_dev(dev)                          # stride 0: one row for every step
-        else:
-            pmf = torch.from_numpy(np.ascontiguousarray(rows).view(np.int64).reshape(steps, 1, -1)).to(dev)
         tr = torch.zeros((steps, 1, 2), dtype=torch.int64, device=dev)
-        self._coder.encode(pmf, self._sym_tensor(syms), trace=tr)
+        if isinstance(rows, _FsmRows):                            # the device gathers the rows by state
+            self._coder.encode_fsm(self._sym_tensor(syms), trace=tr)
+        else:
+            if rows.ndim == 1:
+                pmf = self._tab.row_dev(dev)                      # stride 0: one row for every step
+            else:
+                pmf = torch.from_numpy(np.ascontiguousarray(rows).view(np.int64).reshape(steps, 1, -1)).to(dev)
+            self._coder.encode(pmf, self._sym_tensor(syms), trace=tr)
         rc, err, step = self._coder.status()
         t = tr.cpu().numpy()
         # err_step counts symbols since the last reset: the failing one's index in this chunk
@@ -601,6 +708,24 @@ class A_to_bin:
                 yield from self.flush()
             return
         tab = self._tables()
+        model = None if tab.static else self._fsm_tables()
+        if model is not None:
+            syms, bad, bad_sym = self._static_symbols(symbols, model[0].shape[1])
+            if not self._fsm_begin(model, len(syms)):
+                model, symbols = None, syms                    # (symbols may be an iterator: already drawn)
+        if model is not None:
+            # a finite-state model: one launch per capacity chunk, the states advanced on the
+            # device; accept is replayed on the host predictor for the symbols coded
+            digs, (rc, n_ok) = self._encode_rows(_FsmRows(model[0].shape[1]), syms) if len(syms) else ([], (0, 0))
+            for s in syms[:n_ok].tolist():
+                tab.accept(s)
+            for d in digs:
+                yield from d
+            if rc:
+                _raise_for(rc, bad_sym if bad is not None and n_ok == bad else int(syms[n_ok]))
+            if stop:
+                yield from self.flush()
+            return
         if tab.static:
             row = tab.row()
             syms, bad, bad_sym = self._static_symbols(symbols, len(row))
@@ -648,11 +773,43 @@ class A_to_bin:
         self._nsym = 0
         return R, L
 
+    def _encode_fsm_whole(self, tab, model, symbols):
+        """encode(symbols) of a fresh coder on a finite-state model: one launch, flush and
+        carry resolution on the device, as _encode_static_whole."""
+        V = model[0].shape[1]
+        syms, bad, bad_sym = self._static_symbols(symbols, V)
+        n = len(syms) if bad is None else bad
+        self._fsm_begin(model, n)                               # (fresh: it can always load)
+        if n:
+            self._coder.encode_fsm(self._sym_tensor(syms[:n]))
+            rc, err, step = self._coder.status()
+            k = min(max(int(step[0]), 0), n - 1) if rc else n
+            for s in syms[:k].tolist():
+                tab.accept(s)
+            self._nsym = k
+            self._plane_bits = 1                                # registers are mid-stream now
+            if rc:
+                _raise_for(rc, int(syms[k]))
+        if bad is not None:
+            raise AssertionError("unknown symbol", bad_sym)
+        self._coder.finish()
+        data, nbits = self._coder.to_bytes()
+        L = int(nbits[0])
+        R = int.from_bytes(data[0], "big") >> (8 * len(data[0]) - L) if L else 0
+        self.emitted_bits += L
+        self._coder.reset()
+        self._plane_bits = 0
+        self._nsym = 0
+        return R, L
+
     def encode(self, symbols, stop=1):
         if stop and not self.debug_log and not isinstance(self, MappedEncoderMixin) and self._fresh():
             tab = self._tables()
             if tab.static:
                 return self._encode_static_whole(tab, symbols)
+            model = self._fsm_tables()
+            if model is not None:
+                return self._encode_fsm_whole(tab, model, symbols)
         d = np.fromiter(self.run(symbols, stop), dtype=np.int8)
         return digits_value(d), len(d)
 
@@ -758,6 +915,7 @@ class _Session:
         self.st["err_step"] = -1
         self.tst = None                                   # reference frame (tail mode)
         self.stopped_undetermined = False                 # _fast_static stopped before an undetermined symbol
+        self.fsm_on = None                                # the BatchCoder that holds the finite-state model
         if self.tab.uniform:
             # Predictor(n)'s val_to_symbol is not the inverse of its floor
             # symbol_to_range, so emit_symbol's overlap check (arith_code.py:277)
@@ -979,8 +1137,9 @@ class A_from_bin:
             data = np.packbits(np.asarray(bl, dtype=np.uint8)).tobytes()     # group_bits' format
         sess.load_bits(bl, data)
         tab = sess.tab
-        if tab.static:
-            yield from self._fast_static(sess, max_symbols)
+        model = None if tab.static else _fsm_model(self.predictor)
+        if tab.static or model is not None:
+            yield from self._fast_static(sess, max_symbols, model)
             if not sess.stopped_undetermined:          # (else decide() would find the same)
                 yield from sess.decide()
             return
@@ -1000,33 +1159,46 @@ class A_from_bin:
             yield s
         yield from sess.decide()                   # undetermined: nothing; window off [l, h]: the reference's way
 
-    def _fast_static(self, sess, max_symbols):
-        """Determined symbols of a static model in a few launches: chunks of
+    def _fast_static(self, sess, max_symbols, model=None):
+        """Determined symbols of a static model -- or, with ``model`` (``_fsm_model``), of a
+        finite-state one, whose states the device advances (BatchCoder.decode_fsm) and whose
+        ``accept`` is replayed on the host predictor -- in a few launches: chunks of
         stride-0 steps (doubling) decoded with LAC_OPT_DECODE_STOP, so the stream
         stops by itself before the first symbol the bits do not determine (or whose
         window leaves [l, h]) with the registers of that point: the session parks
         exactly where the per-symbol loop would, and nothing is decoded twice (round
         5 replayed the last chunk up to that point: every symbol decoded twice)."""
         tab = sess.tab
-        row = tab.row()
-        V = len(row)
+        if model is None:
+            row = tab.row()
+            V = len(row)
+        else:
+            V = model[0].shape[1]
         c = sess._coder_for(V)
+        if model is not None:
+            if sess.fsm_on is not c:
+                c.load_fsm(model[0], model[1])
+                sess.fsm_on = c
+            c.set_fsm_states([int(self.predictor.s)])
         c.decode_open(sess.dev, sess.nb)
         start = sess.st.copy()
         start["det"] = 1
         check(c.lib.lac_decode_set_state(c.ctx, start.ctypes.data_as(C.c_void_p), c._stream))
-        pmf = tab.row_dev(c.device).view(1, 1, V)
-        # first chunk: the bits over the table's entropy (+10 %), what a stream drawn
-        # from the table holds; doubling covers the rest, the stop the overshoot
-        p = row[row > 0].astype(np.float64)
-        p /= p.sum()
-        H = float(-(p * np.log2(p)).sum())
+        if model is None:
+            pmf = tab.row_dev(c.device).view(1, 1, V)
+            # first chunk: the bits over the table's entropy (+10 %), what a stream drawn
+            # from the table holds; doubling covers the rest, the stop the overshoot
+            p = row[row > 0].astype(np.float64)
+            p /= p.sum()
+            H = float(-(p * np.log2(p)).sum())
+        else:
+            H = 1.0                                        # (one symbol per bit to begin with)
         done, n = 0, int(min(1 << 20, 64 + 1.1 * len(sess.bits) / max(H, 1e-9)))
         c.set_decode_stop(True)
         try:
             while done < max_symbols:
                 n = min(n, max_symbols - done)
-                out = c.decode(pmf.expand(n, 1, V))
+                out = c.decode(pmf.expand(n, 1, V)) if model is None else c.decode_fsm(n)
                 new = np.zeros(1, dtype=_DEC_STATE)
                 check(c.lib.lac_decode_get_state(c.ctx, new.ctypes.data_as(C.c_void_p), c._stream))
                 err = int(new["err"][0])
@@ -1047,6 +1219,9 @@ class A_from_bin:
                 sess.st = start
                 # a static model's accept is the base no-op (_is_static): the reference calls
                 # it per symbol to no effect, so the symbols go out without the calls
+                if model is not None:
+                    for s in syms:
+                        tab.accept(s)
                 yield from syms
                 done += got
                 if err or got < n:
@@ -1153,6 +1328,29 @@ class A_from_bin:
         out = []
         coder = None
         limit = n if n is not None else max_symbols
+        model = _fsm_model(self.predictor) if n is not None and not tab.static else None
+        if model is not None:                                # a finite-state model: all n symbols in one launch
+            V = model[0].shape[1]
+            coder = BatchCoder(V, 1, prec=self.precision, pmf_bits=64, capacity_bits=max(nbits, 64) + 64)
+            try:
+                coder.load_fsm(model[0], model[1])
+                coder.set_fsm_states([int(self.predictor.s)])
+                stride = ((len(data) + 7) // 8 + 1) * 8
+                buf = np.zeros((1, stride), dtype=np.uint8)
+                buf[0, :len(data)] = np.frombuffer(data, dtype=np.uint8)
+                self._bits = torch.from_numpy(buf).to(coder.device)
+                self._nbits = torch.tensor([nbits], dtype=torch.int64, device=coder.device)
+                coder.decode_open(self._bits, self._nbits)
+                syms = coder.decode_fsm(n)[:, 0].cpu().tolist() if n else []
+                rc, err, step = coder.status()
+                for s in syms[:int(step[0]) if rc else n]:
+                    out.append(s)
+                    tab.accept(s)
+                if rc:
+                    _raise_for(int(err[0]) or _lib.LAC_E_DECODE_RANGE)
+            finally:
+                coder.close()
+            return out
         try:
             for i in range(limit):
                 row = tab.row()

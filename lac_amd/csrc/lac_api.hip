@@ -98,6 +98,9 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->ubits);
     (void)hipFree(c->unbits);
     (void)hipFree(c->wbase);
+    (void)hipFree(c->fsm);
+    (void)hipFree(c->fsm_state);
+    (void)hipFree(c->fsm_flag);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;

@@ -1657,6 +1657,7 @@ int lac_decode_open(lac_ctx *c, const uint8_t *bits_dev, uint64_t stride_bytes, 
     c->dnbits = nbits_dev;
     c->mode = 1;
     c->wsrc = nullptr;                                        // (lac_decode_open_window sets it after this open)
+    c->fsm_busy = 0;                                          // (a new decode job: lac_fsm_load is free again)
     k_dec_init<<<(unsigned)((c->B + 255) / 256), 256, 0, S(stream)>>>(c->dec, c->B, c->prec, bits_dev, stride_bytes,
                                                                       nbits_dev);
     CHECK_LAUNCH();

@@ -867,6 +867,7 @@ int lac_encode_reset(lac_ctx *c, void *stream) {
     c->mode = 0;
     c->finished = 0;
     c->open = 0;
+    c->fsm_busy = 0;
     k_enc_reset<<<(unsigned)((c->B + 255) / 256), 256, 0, S(stream)>>>(c->enc, c->B, c->prec);
     CHECK_LAUNCH();
     return LAC_OK;

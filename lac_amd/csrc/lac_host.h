@@ -9,6 +9,7 @@
 
 #include "lac_dev.h"
 #include "lac_select.h"
+#include "lac_fsm.h"
 
 // ====================================================================== C-ABI
 struct lac_ctx {
@@ -74,6 +75,13 @@ struct lac_ctx {
     int64_t xch_abort = -1;             // word of pxch holding the last row-group launch's abort flag
     int64_t *slen = nullptr;            // lac_set_stream_lengths: [B] per-stream symbol counts (the context's copy)
     bool has_len = false;               //                         counts are set (kernels get slen, else nullptr)
+    // finite-state models (lac_fsm_load, lac_fsm.hip): the prepared model (lac_fsm.h), one allocation
+    void *fsm = nullptr;
+    FsmLayout fsm_y = {};
+    bool fsm_has_next = false;
+    int32_t *fsm_state = nullptr;       //   [B] every stream's current state, kept across calls
+    int *fsm_flag = nullptr;            //   the load's verdict on `next` (an entry outside [0, K))
+    int fsm_busy = 0;                   //   an lac_fsm_decode ran since the last lac_decode_open: mid-job
     // live kernel timing (lac_profile_enable): hipEvent pairs around launches
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
