@@ -554,6 +554,49 @@ int lac_fsm_encode(lac_ctx *ctx, const int32_t *sym_dev, const int32_t *states_d
                    uint64_t *trace_dev, void *stream);
 int lac_fsm_decode(lac_ctx *ctx, const int32_t *states_dev, int64_t steps, int32_t *sym_out_dev, void *stream);
 
+/* ---- adaptive n-gram count models (the reference's Markov_up_to_n, arith_code.py:443-464) ----
+ * A model that learns while it codes: V symbols (the context's), an order k in [1, 4] and integer
+ * weights W[0..k-1] < 2^30.  Stream b keeps `past`, its last <= k accepted symbols, and one u32
+ * count per n-gram of length i + 1 (i < k), all 0 at the start.  With m = len(past) the table of a
+ * step is  pmf[s] = 1 + sum_{i<m} W[i] * C_i[(last i symbols of past), s]  (Markov_up_to_n.prob,
+ * :460-462, with lfunc(c, o, n, order) == c * W[o]), and accepting s adds 1 to those m counts and
+ * appends s to past (accept, :454-459).  Step t codes with that row exactly as lac_encode /
+ * lac_decode_steps code it -- ceil mapping, fudged rows included -- so per stream everything
+ * (bytes, nbits, registers, decoded symbols, status codes and err_step) is what the pmf path gives
+ * on the rows the counts produce.  One kernel launch per call whatever the steps; the launches
+ * report under lac_profile_read's slots 1 (encode) and 3 (decode_step).
+ *
+ * lac_count_load  (Markov_up_to_n.__init__, :444-449) allocates streams x stride counts, zeroed,
+ *   and empties every past; weights_host: `order` host integers.  LAC_E_ARG: V > 4096, order
+ *   outside [1, 4], sum_{i<order} V^(i+1) > 2^25 counts per stream (an order-3 byte model fits), a
+ *   weight >= 2^30, LAC_MAP_FLOOR.  Only between jobs (LAC_E_STATE, lac_fsm_load's rule).  A
+ *   context holds a finite-state model and a count model independently; lac_close frees both.
+ * lac_count_layout  (:447, the dict `table` as a dense array) out[6] = {Vc, stride_words, off[4]}:
+ *   stream b's counts are words [b * stride, (b + 1) * stride); section i (i < order) starts at
+ *   word off[i] and holds V^i rows of Vc = 4 ceil(V / 4) counts; the row of a context is its i
+ *   symbols read oldest first as base-V digits (lac_amd/csrc/lac_count.h).
+ * lac_count_set_state / lac_count_get_state  (:447-448, `table` and `past`) every stream's counts
+ *   (uint32 [streams][stride], device; NULL sets all to 0) and past (int32 [streams][order],
+ *   most recent last, -1 absent; NULL: empty), copied on `stream`.  A stream's valid history is
+ *   its trailing run of entries in [0, V).  Either output of get_state may be NULL.
+ * lac_count_encode  (A_to_bin.step with prob + accept, :187-192, :454-462) continues the open encode
+ *   like lac_encode: sym_dev int32 [steps][streams], trace_dev as lac_encode's or NULL.
+ * lac_count_decode  (A_from_bin.step, :264-299, :454-462) after any lac_decode_open*: sym_out_dev
+ *   int32 [steps][streams] (-1 after an error); honours lac_decode_refill between calls,
+ *   LAC_OPT_DECODE_STOP and lac_decode_determined.
+ * Sticky errors are the pmf path's on the row the counts produce, with its precedence: an entry
+ * that does not fit pmf_bits or a total >= 2^64 is LAC_E_TABLE at that step (u32 rows whose total
+ * passes 2^32 are legal), as is a count that would pass 2^32 - 1.  A failed step updates no count
+ * and does not move past.  Both coding calls honour lac_set_stream_lengths.  Refused before
+ * anything is launched: LAC_E_STATE with no count model loaded, under LAC_MAP_FLOOR or in the
+ * wrong mode. */
+int lac_count_load(lac_ctx *ctx, int order, const uint32_t *weights_host, void *stream);
+int lac_count_layout(lac_ctx *ctx, int64_t *out);
+int lac_count_set_state(lac_ctx *ctx, const uint32_t *counts_dev, const int32_t *past_dev, void *stream);
+int lac_count_get_state(lac_ctx *ctx, uint32_t *counts_dev_out, int32_t *past_dev_out, void *stream);
+int lac_count_encode(lac_ctx *ctx, const int32_t *sym_dev, int64_t steps, uint64_t *trace_dev, void *stream);
+int lac_count_decode(lac_ctx *ctx, int64_t steps, int32_t *sym_out_dev, void *stream);
+
 /* ---- logits path --------------------------------
  * Tables are computed in-kernel from raw logits with the integer-exact "q1"
  * quantiser instead of being read from a pmf in HBM: for each row

@@ -81,6 +81,12 @@ PROTOTYPES = [
     ("lac_fsm_get_states", _i, [_vp, _vp, _vp]),
     ("lac_fsm_encode", _i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     ("lac_fsm_decode", _i, [_vp, _vp, _i64, _vp, _vp]),
+    ("lac_count_load", _i, [_vp, _i, _vp, _vp]),
+    ("lac_count_layout", _i, [_vp, _vp]),
+    ("lac_count_set_state", _i, [_vp, _vp, _vp, _vp]),
+    ("lac_count_get_state", _i, [_vp, _vp, _vp, _vp]),
+    ("lac_count_encode", _i, [_vp, _vp, _i64, _vp, _vp]),
+    ("lac_count_decode", _i, [_vp, _i64, _vp, _vp]),
     ("lac_decode_get_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_set_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_tail_begin", _i, [_vp, _vp]),

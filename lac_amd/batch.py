@@ -679,6 +679,107 @@ class BatchCoder:
                                       C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    # ------------------------------------------------------------ adaptive count models
+    def load_counts(self, order, weights):
+        """Load an adaptive n-gram count model (include/lac.h lac_count_load; the reference's
+        Markov_up_to_n, arith_code.py:443-464, with lfunc(c, o, n, order) == c * weights[o]):
+        every stream gets zeroed counts and an empty past.  Only between jobs.  1 <= order <= 4,
+        vocab <= 4096, sum vocab^(i+1) <= 2^25 counts per stream, weights < 2^30."""
+        order = int(order)
+        w = [int(x) for x in weights]
+        if len(w) != order:
+            raise ValueError(f"give {order} weights, got {len(w)}")
+        if any(x < 0 or x >= 1 << 32 for x in w):
+            raise ValueError("weights must be in [0, 2^30)")
+        arr = (C.c_uint32 * max(order, 1))(*w)
+        check(self.lib.lac_count_load(self.ctx, order, arr, self._stream))
+        out = (C.c_int64 * 6)()
+        check(self.lib.lac_count_layout(self.ctx, out))
+        self.count_order = order
+        self.count_weights = w
+        self.count_layout = {"Vc": int(out[0]), "stride": int(out[1]), "off": [int(out[2 + i]) for i in range(order)]}
+
+    def _need_counts(self):
+        if getattr(self, "count_layout", None) is None:
+            from ._lib import LacError, LAC_E_STATE
+            raise LacError(LAC_E_STATE, "no count model: call load_counts first")
+
+    def set_count_state(self, counts=None, past=None):
+        """Every stream's counts (uint32 [streams, stride] in the layout of ``count_layout``,
+        numpy or a device int32 / uint32 tensor; None: all zero) and past ([streams, order]
+        integers, most recent last, -1 absent; None: empty).  Copied."""
+        torch = _torch()
+        self._need_counts()
+        cd = pd = None
+        if counts is not None:
+            if isinstance(counts, torch.Tensor):
+                cd = counts.to(self.device).contiguous()
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32).view(np.int32)).to(self.device)
+            if cd.element_size() != 4 or cd.numel() != self.streams * self.count_layout["stride"]:
+                raise ValueError(f"counts must be 32-bit [{self.streams}, {self.count_layout['stride']}]")
+        if past is not None:
+            arr = past.detach().cpu().numpy() if isinstance(past, torch.Tensor) else np.asarray(past)
+            if arr.size != self.streams * self.count_order:
+                raise ValueError(f"past must be [{self.streams}, {self.count_order}]")
+            pd = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(self.device)
+        check(self.lib.lac_count_set_state(self.ctx, None if cd is None else C.c_void_p(cd.data_ptr()),
+                                           None if pd is None else C.c_void_p(pd.data_ptr()), self._stream))
+        self._count_keep = (cd, pd)
+
+    def count_state(self, device=False):
+        """-> (counts uint32 [streams, stride], past int32 [streams, order]) as numpy arrays, or
+        (``device=True``) as device tensors (counts as int32 bit patterns); synchronises."""
+        torch = _torch()
+        self._need_counts()
+        counts = torch.empty((self.streams, self.count_layout["stride"]), dtype=torch.int32, device=self.device)
+        past = torch.empty((self.streams, self.count_order), dtype=torch.int32, device=self.device)
+        check(self.lib.lac_count_get_state(self.ctx, C.c_void_p(counts.data_ptr()), C.c_void_p(past.data_ptr()),
+                                           self._stream))
+        if device:
+            torch.cuda.current_stream(self.device).synchronize()
+            return counts, past
+        return counts.cpu().numpy().view(np.uint32), past.cpu().numpy()
+
+    def encode_counts(self, sym, trace=None):
+        """Continue every stream by ``sym`` [steps, streams] (int32 device tensor) under the
+        loaded count model, in one launch: step t codes with the row the stream's counts give
+        and then counts the symbol.  Bit for bit :meth:`encode` on those rows; ``trace`` as
+        there."""
+        torch = _torch()
+        if sym.dtype != torch.int32 or sym.device != self.device:
+            raise TypeError("sym must be an int32 tensor on the coder's device")
+        sym = sym.contiguous()
+        steps = sym.shape[0] if sym.dim() == 2 else 1
+        if sym.numel() != steps * self.streams:
+            raise ValueError(f"sym must be [steps, {self.streams}]")
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int64 or trace.numel() != steps * self.streams * 2 or not trace.is_contiguous():
+                raise ValueError("trace must be a contiguous int64 tensor [steps, streams, 2]")
+            tp = C.c_void_p(trace.data_ptr())
+        self._keep = (sym,)
+        check(self.lib.lac_count_encode(self.ctx, C.c_void_p(sym.data_ptr()), steps, tp, self._stream))
+
+    def encode_counts_job(self, sym):
+        """reset + set_count_state() (zero counts, empty past) + encode_counts + finish."""
+        self.reset()
+        self.set_count_state()
+        self.encode_counts(sym)
+        self.finish()
+
+    def decode_counts(self, steps, out=None):
+        """Decode ``steps`` symbols per stream under the loaded count model in one launch (after
+        any decode_open*), from the counts and past the streams hold.  -> int32 [steps, streams]."""
+        torch = _torch()
+        steps = int(steps)
+        if out is None:
+            out = torch.empty((steps, self.streams), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out(out, steps)
+        check(self.lib.lac_count_decode(self.ctx, steps, C.c_void_p(out.data_ptr()), self._stream))
+        return out
+
     # ------------------------------------------------------------ logits path
     def _logits_args(self, logits, steps=None):
         """-> (type, step_stride, stream_stride, steps) for a [steps, streams, V]

@@ -168,6 +168,58 @@ class NFA(ProbPredictor):
         return NFA(self.s, self.t)
 
 
+class CountWeights:
+    """``lfunc`` of a Markov_up_to_n that is linear in the count: ``(c, o, n, m) -> c * weights[o]``.
+    It carries ``weights``, which is what lets A_to_bin / A_from_bin hand the model to liblac's
+    count-model kernels (``_count_model``)."""
+
+    def __init__(self, weights):
+        self.weights = tuple(int(w) for w in weights)
+
+    def __call__(self, c, o, n, m):
+        return c * self.weights[o]
+
+
+class Markov_up_to_n(ProbPredictor):
+    """Adaptive n-gram predictor (arith_code.py:443-464): ``table`` counts every n-gram of
+    length <= ``order`` seen so far (a dict from the n-gram tuple, context then symbol), ``past``
+    holds the last <= ``order`` accepted symbols, and with m = len(past)
+
+        prob(s) = 1 + sum_{i < m} lfunc(table[(last i symbols of past) + (s,)], i, n, order)
+
+    ``accept(s)`` adds 1 to those m n-grams (m taken before the update) and appends s to past.
+    ``lfunc=None`` is ``CountWeights([n * o**3 for o in range(order)])``, the reference's default
+    ``c*n*o**3``; with a CountWeights the coders run the model on the device in one launch per
+    job, any other callable is coded per token."""
+
+    def __init__(self, n, order, lfunc=None, past=(), table=None):
+        super().__init__(n)
+        self.order = order
+        self.table = table if table is not None else {}
+        self.past = tuple(past)
+        self.lfunc = lfunc if lfunc is not None else CountWeights([n * o ** 3 for o in range(order)])
+
+    def __getitem__(self, k):
+        return self.table.get(k, 0)
+
+    def __setitem__(self, k, v):
+        self.table[k] = v
+
+    def accept(self, symbol):
+        gram = self.past + (symbol,)
+        for i in range(len(self.past)):
+            self[gram[-i - 1:]] += 1
+        self.past = gram[-self.order:]
+        return super().accept(symbol)
+
+    def prob(self, symbol):
+        gram = self.past + (symbol,)
+        return 1 + sum(self.lfunc(self[gram[-i - 1:]], i, self.n, self.order) for i in range(len(self.past)))
+
+    def copy(self):
+        return type(self)(self.n, self.order, self.lfunc, self.past, dict(self.table))   # (a subclass stays one)
+
+
 ternary = Predictor(3)
 
 
@@ -343,13 +395,113 @@ def _fsm_model_still(predictor):
         and isinstance(getattr(predictor, "s", None), (int, np.integer)) and 0 <= int(predictor.s) < len(predictor.t)
 
 
-class _FsmRows:
-    """Stands for the rows of a finite-state job in A_to_bin._encode_rows: the device gathers
-    them itself (BatchCoder.encode_fsm), one 'static row' of V entries as far as chunking goes."""
+def _count_model(predictor):
+    """(V, order, weights) when ``predictor`` is Markov_up_to_n (arith_code.py:443-464) as liblac's
+    count-model kernels can code it, else None: its ``prob``, ``accept`` and ``calc_dist`` resolve
+    to the class's own (a subclass overriding one keeps the per-token path), its mapping is
+    CDFPredictor's, it declares no ``minp`` of its own, its ``lfunc`` is a CountWeights, and the
+    model is within the kernels' limits (include/lac.h lac_count_load)."""
+    for m, q in (("prob", "Markov_up_to_n.prob"), ("accept", "Markov_up_to_n.accept"),
+                 ("calc_dist", "ProbPredictor.calc_dist")):
+        if _impl(predictor, m) not in ((q, mod) for mod in _REF_MODULES):
+            return None
+    if not _is_table(predictor) or _declared_minp(predictor) is not None:
+        return None
+    f = getattr(predictor, "lfunc", None)
+    try:
+        V, order = int(predictor.n), int(predictor.order)
+        if not isinstance(f, CountWeights) or not 1 <= order <= 4 or not 1 <= V <= 4096 or len(f.weights) < order:
+            return None
+        if sum(V ** (i + 1) for i in range(order)) > 1 << 25 or any(not 0 <= w < 1 << 30 for w in f.weights[:order]):
+            return None
+        if not isinstance(predictor.table, dict) or len(predictor.past) > order:
+            return None
+        if any(not 0 <= int(x) < V for x in predictor.past):
+            return None
+    except (TypeError, ValueError, AttributeError):
+        return None
+    return V, order, tuple(f.weights[:order])
+
+
+class _FsmJob:
+    """A finite-state model (``_fsm_model``) as a model the device advances itself: how the
+    coders load it, hand over the predictor's state, and code with it."""
+
+    def __init__(self, tables, nxt):
+        self.tables, self.next = tables, nxt
+        self.V = tables.shape[1]
+        self.key = ("fsm", id(tables))
+
+    def load(self, coder):
+        coder.load_fsm(self.tables, self.next)
+
+    def begin(self, coder, predictor):
+        coder.set_fsm_states([int(predictor.s)])
+
+    def encode(self, coder, sym, trace=None):
+        coder.encode_fsm(sym, trace=trace)
+
+    def decode(self, coder, n):
+        return coder.decode_fsm(n)
+
+
+class _CountJob:
+    """An adaptive count model (``_count_model``) as a model the device advances itself.  The
+    predictor object stays the truth: before a job its ``table`` and ``past`` go up as dense
+    counts (nothing but zeros for an empty table), after it the coders replay ``accept`` on it for
+    the symbols coded."""
+
+    def __init__(self, V, order, weights):
+        self.V, self.order, self.weights = V, order, weights
+        self.key = ("counts", V, order, weights)
+
+    def load(self, coder):
+        coder.load_counts(self.order, self.weights)
+
+    def begin(self, coder, predictor):
+        past = [-1] * (self.order - len(predictor.past)) + [int(x) for x in predictor.past]
+        counts = None
+        if predictor.table:
+            y, V = coder.count_layout, self.V
+            counts = np.zeros((1, y["stride"]), dtype=np.uint32)
+            for gram, c in predictor.table.items():
+                i = len(gram) - 1
+                if not 0 <= i < self.order or any(not 0 <= int(x) < V for x in gram) or not 0 <= int(c) < 1 << 32:
+                    raise ValueError(f"table entry {gram!r}: {c!r} is no count of an n-gram of this model")
+                row = 0
+                for x in gram[:-1]:
+                    row = row * V + int(x)
+                counts[0, y["off"][i] + row * y["Vc"] + int(gram[-1])] = int(c)
+        coder.set_count_state(counts, [past])
+
+    def encode(self, coder, sym, trace=None):
+        coder.encode_counts(sym, trace=trace)
+
+    def decode(self, coder, n):
+        return coder.decode_counts(n)
+
+
+def _device_model(predictor, fsm=None):
+    """``predictor`` as a model the device advances itself -- a _CountJob or a _FsmJob -- or
+    None.  ``fsm``: a converted finite-state model to reuse (its conversion reads every table)."""
+    cm = _count_model(predictor)
+    if cm is not None:
+        return _CountJob(*cm)
+    if fsm is not None:
+        return fsm if _fsm_model_still(predictor) else None
+    m = _fsm_model(predictor)
+    return None if m is None else _FsmJob(*m)
+
+
+class _ModelRows:
+    """Stands for the rows of a job on a model the device advances (``_device_model``) in
+    A_to_bin._encode_rows: the device finds them itself, one 'static row' of V entries as far as
+    chunking goes."""
     ndim = 1
 
-    def __init__(self, V):
-        self.shape = (V,)
+    def __init__(self, job):
+        self.job = job
+        self.shape = (job.V,)
 
 
 def fudge_decisions_agree(T, minp, min_pos, prec):
@@ -476,29 +628,34 @@ class A_to_bin:
         self._tab = None
         self._plane_bits = 0          # output bits held in the device planes since the last reset
         self._nsym = 0                # symbols coded since the last reset
-        self._fsm = None              # (transitions object, _fsm_model of it): converted once
-        self._fsm_on = None           # the BatchCoder that holds the model
+        self._fsm = None              # (transitions object, _FsmJob of it): converted once
+        self._model_on = None         # (the BatchCoder that holds a model, the model's key)
 
-    def _fsm_tables(self):
-        """The predictor as a finite-state model (``_fsm_model``), or None."""
+    def _model(self):
+        """The predictor as a model the device advances (``_device_model``), or None."""
+        if _count_model(self.predictor) is not None:
+            return _device_model(self.predictor)
         t = getattr(self.predictor, "t", None)
         if self._fsm is None or self._fsm[0] is not t:
-            self._fsm = (t, _fsm_model(self.predictor))
-        return self._fsm[1] if _fsm_model_still(self.predictor) else None
+            m = _fsm_model(self.predictor)
+            self._fsm = (t, None if m is None else _FsmJob(*m))
+        return None if self._fsm[1] is None else _device_model(self.predictor, self._fsm[1])
 
-    def _fsm_begin(self, model, steps):
-        """Coder, model and start state on the device; False when the model cannot be loaded
-        now (the coder is in mid-stream and holds none: the per-token path goes on)."""
-        V = model[0].shape[1]
+    def _model_begin(self, model, steps):
+        """Coder, model and the predictor's state on the device; False when the model cannot be
+        loaded now (the coder is in mid-stream and holds none: the per-token path goes on)."""
+        V = model.V
+        held = self._coder is not None and self._model_on is not None and self._model_on[0] is self._coder \
+            and self._model_on[1] == model.key
         if self._coder is not None and self._V != V and not self._fresh():
             return False
-        if self._coder is not None and self._fsm_on is not self._coder and not self._fresh():
+        if self._coder is not None and not held and not self._fresh():
             return False
         self._ensure(V, steps)
-        if self._fsm_on is not self._coder:
-            self._coder.load_fsm(model[0], model[1])
-            self._fsm_on = self._coder
-        self._coder.set_fsm_states([int(self.predictor.s)])
+        if self._model_on is None or self._model_on[0] is not self._coder or self._model_on[1] != model.key:
+            model.load(self._coder)
+            self._model_on = (self._coder, model.key)
+        model.begin(self._coder, self.predictor)
         return True
 
     def _tables(self, begin=True):
@@ -581,8 +738,8 @@ class A_to_bin:
         steps = len(syms)
         dev = self._coder.device
         tr = torch.zeros((steps, 1, 2), dtype=torch.int64, device=dev)
-        if isinstance(rows, _FsmRows):                            # the device gathers the rows by state
-            self._coder.encode_fsm(self._sym_tensor(syms), trace=tr)
+        if isinstance(rows, _ModelRows):                          # the device finds the rows itself
+            rows.job.encode(self._coder, self._sym_tensor(syms), trace=tr)
         else:
             if rows.ndim == 1:
                 pmf = self._tab.row_dev(dev)                      # stride 0: one row for every step
@@ -708,15 +865,15 @@ class A_to_bin:
                 yield from self.flush()
             return
         tab = self._tables()
-        model = None if tab.static else self._fsm_tables()
+        model = None if tab.static else self._model()
         if model is not None:
-            syms, bad, bad_sym = self._static_symbols(symbols, model[0].shape[1])
-            if not self._fsm_begin(model, len(syms)):
+            syms, bad, bad_sym = self._static_symbols(symbols, model.V)
+            if not self._model_begin(model, len(syms)):
                 model, symbols = None, syms                    # (symbols may be an iterator: already drawn)
         if model is not None:
-            # a finite-state model: one launch per capacity chunk, the states advanced on the
-            # device; accept is replayed on the host predictor for the symbols coded
-            digs, (rc, n_ok) = self._encode_rows(_FsmRows(model[0].shape[1]), syms) if len(syms) else ([], (0, 0))
+            # a model the device advances: one launch per capacity chunk, the state or the counts
+            # kept on the device; accept is replayed on the host predictor for the symbols coded
+            digs, (rc, n_ok) = self._encode_rows(_ModelRows(model), syms) if len(syms) else ([], (0, 0))
             for s in syms[:n_ok].tolist():
                 tab.accept(s)
             for d in digs:
@@ -773,15 +930,15 @@ class A_to_bin:
         self._nsym = 0
         return R, L
 
-    def _encode_fsm_whole(self, tab, model, symbols):
-        """encode(symbols) of a fresh coder on a finite-state model: one launch, flush and
-        carry resolution on the device, as _encode_static_whole."""
-        V = model[0].shape[1]
+    def _encode_model_whole(self, tab, model, symbols):
+        """encode(symbols) of a fresh coder on a model the device advances: one launch, flush
+        and carry resolution on the device, as _encode_static_whole."""
+        V = model.V
         syms, bad, bad_sym = self._static_symbols(symbols, V)
         n = len(syms) if bad is None else bad
-        self._fsm_begin(model, n)                               # (fresh: it can always load)
+        self._model_begin(model, n)                             # (fresh: it can always load)
         if n:
-            self._coder.encode_fsm(self._sym_tensor(syms[:n]))
+            model.encode(self._coder, self._sym_tensor(syms[:n]))
             rc, err, step = self._coder.status()
             k = min(max(int(step[0]), 0), n - 1) if rc else n
             for s in syms[:k].tolist():
@@ -807,9 +964,9 @@ class A_to_bin:
             tab = self._tables()
             if tab.static:
                 return self._encode_static_whole(tab, symbols)
-            model = self._fsm_tables()
+            model = self._model()
             if model is not None:
-                return self._encode_fsm_whole(tab, model, symbols)
+                return self._encode_model_whole(tab, model, symbols)
         d = np.fromiter(self.run(symbols, stop), dtype=np.int8)
         return digits_value(d), len(d)
 
@@ -915,7 +1072,7 @@ class _Session:
         self.st["err_step"] = -1
         self.tst = None                                   # reference frame (tail mode)
         self.stopped_undetermined = False                 # _fast_static stopped before an undetermined symbol
-        self.fsm_on = None                                # the BatchCoder that holds the finite-state model
+        self.model_on = None                              # (the BatchCoder that holds a model, the model's key)
         if self.tab.uniform:
             # Predictor(n)'s val_to_symbol is not the inverse of its floor
             # symbol_to_range, so emit_symbol's overlap check (arith_code.py:277)
@@ -1137,7 +1294,7 @@ class A_from_bin:
             data = np.packbits(np.asarray(bl, dtype=np.uint8)).tobytes()     # group_bits' format
         sess.load_bits(bl, data)
         tab = sess.tab
-        model = None if tab.static else _fsm_model(self.predictor)
+        model = None if tab.static else _device_model(self.predictor)
         if tab.static or model is not None:
             yield from self._fast_static(sess, max_symbols, model)
             if not sess.stopped_undetermined:          # (else decide() would find the same)
@@ -1160,8 +1317,8 @@ class A_from_bin:
         yield from sess.decide()                   # undetermined: nothing; window off [l, h]: the reference's way
 
     def _fast_static(self, sess, max_symbols, model=None):
-        """Determined symbols of a static model -- or, with ``model`` (``_fsm_model``), of a
-        finite-state one, whose states the device advances (BatchCoder.decode_fsm) and whose
+        """Determined symbols of a static model -- or, with ``model`` (``_device_model``), of one
+        the device advances itself (BatchCoder.decode_fsm / decode_counts) and whose
         ``accept`` is replayed on the host predictor -- in a few launches: chunks of
         stride-0 steps (doubling) decoded with LAC_OPT_DECODE_STOP, so the stream
         stops by itself before the first symbol the bits do not determine (or whose
@@ -1173,13 +1330,13 @@ class A_from_bin:
             row = tab.row()
             V = len(row)
         else:
-            V = model[0].shape[1]
+            V = model.V
         c = sess._coder_for(V)
         if model is not None:
-            if sess.fsm_on is not c:
-                c.load_fsm(model[0], model[1])
-                sess.fsm_on = c
-            c.set_fsm_states([int(self.predictor.s)])
+            if sess.model_on is None or sess.model_on[0] is not c or sess.model_on[1] != model.key:
+                model.load(c)
+                sess.model_on = (c, model.key)
+            model.begin(c, self.predictor)
         c.decode_open(sess.dev, sess.nb)
         start = sess.st.copy()
         start["det"] = 1
@@ -1198,7 +1355,7 @@ class A_from_bin:
         try:
             while done < max_symbols:
                 n = min(n, max_symbols - done)
-                out = c.decode(pmf.expand(n, 1, V)) if model is None else c.decode_fsm(n)
+                out = c.decode(pmf.expand(n, 1, V)) if model is None else model.decode(c, n)
                 new = np.zeros(1, dtype=_DEC_STATE)
                 check(c.lib.lac_decode_get_state(c.ctx, new.ctypes.data_as(C.c_void_p), c._stream))
                 err = int(new["err"][0])
@@ -1328,20 +1485,20 @@ class A_from_bin:
         out = []
         coder = None
         limit = n if n is not None else max_symbols
-        model = _fsm_model(self.predictor) if n is not None and not tab.static else None
-        if model is not None:                                # a finite-state model: all n symbols in one launch
-            V = model[0].shape[1]
+        model = _device_model(self.predictor) if n is not None and not tab.static else None
+        if model is not None:                                # a model the device advances: all n symbols in one launch
+            V = model.V
             coder = BatchCoder(V, 1, prec=self.precision, pmf_bits=64, capacity_bits=max(nbits, 64) + 64)
             try:
-                coder.load_fsm(model[0], model[1])
-                coder.set_fsm_states([int(self.predictor.s)])
+                model.load(coder)
+                model.begin(coder, self.predictor)
                 stride = ((len(data) + 7) // 8 + 1) * 8
                 buf = np.zeros((1, stride), dtype=np.uint8)
                 buf[0, :len(data)] = np.frombuffer(data, dtype=np.uint8)
                 self._bits = torch.from_numpy(buf).to(coder.device)
                 self._nbits = torch.tensor([nbits], dtype=torch.int64, device=coder.device)
                 coder.decode_open(self._bits, self._nbits)
-                syms = coder.decode_fsm(n)[:, 0].cpu().tolist() if n else []
+                syms = model.decode(coder, n)[:, 0].cpu().tolist() if n else []
                 rc, err, step = coder.status()
                 for s in syms[:int(step[0]) if rc else n]:
                     out.append(s)

@@ -101,6 +101,9 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->fsm);
     (void)hipFree(c->fsm_state);
     (void)hipFree(c->fsm_flag);
+    (void)hipFree(c->cnt);
+    (void)hipFree(c->cnt_past);
+    (void)hipFree(c->cnt_row);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;
