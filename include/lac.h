@@ -586,8 +586,9 @@ int lac_fsm_decode(lac_ctx *ctx, const int32_t *states_dev, int64_t steps, int32
  *   LAC_OPT_DECODE_STOP and lac_decode_determined.
  * Sticky errors are the pmf path's on the row the counts produce, with its precedence: an entry
  * that does not fit pmf_bits or a total >= 2^64 is LAC_E_TABLE at that step (u32 rows whose total
- * passes 2^32 are legal), as is a count that would pass 2^32 - 1.  A failed step updates no count
- * and does not move past.  Both coding calls honour lac_set_stream_lengths.  Refused before
+ * passes 2^32 are legal), as is a count that would pass 2^32 - 1.  That last verdict needs the
+ * symbol, so a decode step reaches it after the register and range tests (LAC_E_DECODE_RANGE), an
+ * encode step after the symbol's range test.  A failed step updates no count and does not move past.  Both coding calls honour lac_set_stream_lengths.  Refused before
  * anything is launched: LAC_E_STATE with no count model loaded, under LAC_MAP_FLOOR or in the
  * wrong mode. */
 int lac_count_load(lac_ctx *ctx, int order, const uint32_t *weights_host, void *stream);

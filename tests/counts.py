@@ -1,10 +1,12 @@
 """The adaptive n-gram count models restated on the host (include/lac.h lac_count_*; helper of
-tests/test_counts_host.py, tests/test_gpu_counts.py and tests/test_gpu_counts_dropin.py).
+tests/test_counts_host.py, tests/test_gpu_counts.py, tests/test_gpu_counts_limits.py and
+tests/test_gpu_counts_dropin.py).
 
 A model: V symbols, an order k in [1, 4], integer weights W[0..k-1].  A stream keeps ``past``,
 its last <= k accepted symbols, and one count per n-gram of length i + 1 (i < k).  With
 m = len(past):  row[s] = 1 + sum_{i<m} W[i] * C_i[(last i symbols of past), s];  accept(s) adds 1
-to those m counts and appends s to past.  The counts are held dense, in the layout the device
+to those m counts and appends s to past -- unless one of them is 0xffffffff: then the step is
+refused and nothing changes.  The counts are held dense, in the layout the device
 uses (lac_amd/csrc/lac_count.h): per stream ``stride`` uint32 words, section i at word off[i],
 V^i rows of Vc = 4 ceil(V / 4) counts, the row of a context its symbols read oldest first as
 base-V digits.
@@ -13,6 +15,7 @@ import numpy as np
 
 # the non-linear lfuncs of the fixtures, by name (tools/gen_golden_markov.py)
 LFUNCS = {"square": lambda c, o, n, m: c * c * (o + 1) + (7 if c else 0)}
+COUNT_FULL = 0xffffffff                                           # a count here cannot be incremented (kCountFull)
 
 
 def layout(V, order):
@@ -61,9 +64,15 @@ class Stream:
         return out
 
     def accept(self, s):
-        for i in range(len(self.past)):
-            self.counts[self._at(i, s)] += 1
+        """Count s under the m current contexts and append it to past.  False, and nothing
+        changes, when one of those counts is full (count_accept, lac_amd/csrc/lac_count.h)."""
+        at = [self._at(i, s) for i in range(len(self.past))]
+        if any(int(self.counts[a]) == COUNT_FULL for a in at):
+            return False
+        for a in at:
+            self.counts[a] += 1
         self.past = (self.past + (int(s),))[-self.order:]
+        return True
 
     def past_row(self):
         """past as the device holds it: [order], most recent last, -1 absent."""
@@ -99,15 +108,17 @@ def pmf_rows(rows, bits, V=None):
 def walk(V, order, W, syms, bits=32, counts=None, past=(), extra_row=False):
     """One stream: the rows [T (+ 1), V] its symbols are coded with, and the Stream afterwards.  A
     symbol outside [0, V) ends the walk there (the stream fails at that step, nothing moves);
-    the rows after it repeat the failing step's."""
+    the rows after it repeat the failing step's.  So does a symbol one of whose counts is full:
+    that step's row is the empty row (LAC_E_TABLE there, as for a bad row)."""
     st = Stream(V, order, W, counts, past)
     rows, dead = [], False
     for s in syms:
         rows.append(st.row() if not dead else rows[-1])
         row_ok = max(rows[-1]) < (1 << bits) and sum(rows[-1]) < (1 << 64)
-        if not dead and 0 <= s < V and row_ok:
-            st.accept(s)
-        else:
+        if dead or not (0 <= s < V and row_ok):
+            dead = True
+        elif not st.accept(s):
+            rows[-1] = [0] * V
             dead = True
     if extra_row:
         rows.append(st.row())

@@ -54,8 +54,9 @@ std::vector<E> row_with_total(Rng &r, int64_t V, uint64_t target) {
     return row;
 }
 
+// every_bound: the search is probed at c_i - 1, c_i and T - 1 for every positive entry too
 template <typename E>
-void check_row(Rng &r, const std::vector<E> &row, int64_t V) {
+void check_row(Rng &r, const std::vector<E> &row, int64_t V, bool every_bound = false) {
     const FsmLayout y = fsm_layout(1, V, 8 * (int)sizeof(E), false);
     EXPECT(y.Vp >= V && y.Vp < V + y.vec && y.Vp % y.vec == 0 && y.nvec * y.vec == y.Vp, "padding V=%lld", (long long)V);
     EXPECT(y.G * 64 >= y.nvec && (y.G - 1) * 64 < y.nvec, "chunking V=%lld", (long long)V);
@@ -93,8 +94,18 @@ void check_row(Rng &r, const std::vector<E> &row, int64_t V) {
         c += row[(size_t)s];
     }
     for (int64_t i = V; i < y.Vp; i++) EXPECT((uint64_t)cdf[(size_t)i] == (uint64_t)T, "CDF padding");
-    for (int k = 0; k < 24; k++) {                             // the decoder's search against bisect_right
-        const uint64_t tgt = k == 0 ? 0 : (k == 1 ? (uint64_t)T - 1 : r.below((uint64_t)T));
+    std::vector<uint64_t> targets;
+    for (int k = 0; k < 24; k++) targets.push_back(k == 0 ? 0 : (k == 1 ? (uint64_t)T - 1 : r.below((uint64_t)T)));
+    if (every_bound) {
+        c = 0;
+        for (int64_t i = 0; i < V; i++) {
+            if (!row[(size_t)i]) continue;
+            c += row[(size_t)i];                               // c_i: the first target past entry i
+            targets.push_back(c - 1);
+            if (c < (uint64_t)T) targets.push_back(c);
+        }
+    }
+    for (const uint64_t tgt : targets) {                       // the decoder's search against bisect_right
         int64_t want = 0;
         uint64_t cc = 0;
         for (int64_t i = 0; i < V; i++) {
@@ -105,6 +116,37 @@ void check_row(Rng &r, const std::vector<E> &row, int64_t V) {
         EXPECT(got == want && got < V, "search tgt=%llu V=%lld: %lld, want %lld", (unsigned long long)tgt, (long long)V,
                (long long)got, (long long)want);
     }
+}
+
+// A sparse row of a long-row layout: at most 8 positive entries, on both sides of a chunk bound,
+// of a second chunk bound at least two whole zero chunks on, and of a 16-B vector bound inside a
+// chunk, plus entries 0 and V - 1; `drop` (a bit per position) leaves some out, so a zero run
+// crosses a bound, starts the row or reaches its end.
+template <typename E>
+void check_sparse_row(Rng &r, int64_t V, unsigned drop) {
+    const FsmLayout y = fsm_layout(1, V, 8 * (int)sizeof(E), false);
+    const int64_t CE = y.G * y.vec, chunks = (y.Vp + CE - 1) / CE;
+    EXPECT(y.long_rows && chunks >= 6, "sparse rows need a long-row layout, V=%lld", (long long)V);
+    if (!y.long_rows || chunks < 6) return;
+    const int64_t c1 = 1 + (int64_t)r.below((uint64_t)(chunks - 5)), c2 = c1 + 3;   // chunks c1 + 1, c1 + 2: all zero
+    const int64_t vb = (chunks - 1) * CE + y.vec;              // a vector bound inside the last chunk, if it has one
+    int64_t at[8] = {0, c1 * CE - 1, c1 * CE, c2 * CE - 1, c2 * CE, vb - 1, vb, V - 1};
+    if (y.G < 2 || vb >= V - 1) at[5] = at[6] = (c2 + 1) * CE - 1 < V ? c2 * CE + y.vec : V - 1;
+    std::vector<E> row((size_t)V, (E)0);
+    int n = 0;
+    for (int k = 0; k < 8; k++)
+        if (!((drop >> k) & 1) && at[k] >= 0 && at[k] < V) {
+            row[(size_t)at[k]] = (E)(1 + r.below(k & 1 ? 1 : 1 << 12));
+            n++;
+        }
+    if (!n) row[(size_t)(c1 * CE)] = 1;
+    int64_t run = 0, longest = 0;                              // (the zero run of two chunks is there)
+    for (int64_t i = 0; i < V; i++) {
+        run = row[(size_t)i] ? 0 : run + 1;
+        longest = run > longest ? run : longest;
+    }
+    EXPECT(longest >= 2 * CE, "zero run of %lld entries, a chunk has %lld", (long long)longest, (long long)CE);
+    check_row<E>(r, row, V, true);
 }
 
 int64_t pick_vocab(Rng &r, int i) {
@@ -161,6 +203,15 @@ int fc_sweep(int rows, uint64_t seed) {
         }
         default: check_row<uint64_t>(r, row_with_total<uint64_t>(r, V, ~(uint64_t)0), V); break;   // 2^64 - 1
         }
+    }
+    // sparse rows of long-row layouts: every position kept, one side of a bound dropped, a row that
+    // ends in a zero run, a row of its first entry alone, then random subsets
+    static const int64_t V32[] = {260, 1000, 4100, 65536}, V64[] = {129, 1000, 65536};
+    static const unsigned drops[] = {0x00, 0x02, 0x04, 0x08, 0x10, 0x80, 0xe0, 0x01, 0xfe, 0x7d, 0xfb, 0x06};
+    for (int i = 0; i < rows / 25; i++) {
+        const unsigned drop = i < 12 ? drops[i] : (unsigned)r.below(256);
+        check_sparse_row<uint32_t>(r, V32[i % 4], drop);
+        check_sparse_row<uint64_t>(r, V64[i % 3], drop);
     }
     return g_fail;
 }

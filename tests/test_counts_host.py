@@ -194,6 +194,48 @@ def test_bad_rows_and_symbols_stop_the_walk(cc):
     assert acc.tolist() == [1, 1, 0, 0] and ps.tolist() == [0, 1] and int(cs.sum()) == 1
 
 
+def _slot(V, order, sec, ctx, s):
+    y = K.layout(V, order)
+    return y["off"][sec] + K.row_index(ctx, V) * y["Vc"] + s
+
+
+@pytest.mark.parametrize("order,sec", ((1, 0), (4, 0), (4, 3)))
+def test_a_full_count_refuses_the_step(cc, order, sec):
+    """Preset counts of 0xfffffffe and 0xffffffff in section `sec`: the first takes one more accept
+    and is then full, the second refuses at once; a refused step changes nothing and ends the walk.
+    ok / acc, the counts and the past of lac_count.h against the restatement's."""
+    V, W, bits = 5, [1, 2, 3, 4][:order], 64
+    a, x, b = 0, 2, 1
+    for past, syms, what in (((3, 1, 4, 2)[-order:], [a, x, b, 3, 3], "a second slot"),
+                             ((a,) * order, [a, a, 4, a], "the same slot")):
+        counts = np.zeros(K.layout(V, order)["stride"], dtype=np.uint32)
+        counts[_slot(V, order, sec, past[order - sec:], a)] = 0xfffffffe
+        if what == "a second slot":
+            after = (tuple(past) + (a, x))[-order:]
+            counts[_slot(V, order, sec, after[order - sec:], b)] = 0xffffffff
+        rows, ok, acc, cs, ps = _c_walk(cc, V, order, W, bits, syms, counts, past)
+        st, want_ok, want_acc, dead = K.Stream(V, order, W, counts, past), [], [], False
+        for t, s in enumerate(syms):
+            r = st.row()
+            assert rows[t].tolist() == r, (what, t)
+            want_ok.append(int(max(r) < 1 << bits and sum(r) < 1 << 64))
+            go = not dead and bool(want_ok[-1]) and st.accept(s)
+            want_acc.append(int(go))
+            dead = dead or not go
+        stop = 2 if what == "a second slot" else 1                # (the restatement itself stops where it was built to)
+        assert want_acc == [1] * stop + [0] * (len(syms) - stop) and all(want_ok), (what, want_acc)
+        assert ok.tolist() == want_ok and acc.tolist() == want_acc, (what, ok, acc)
+        assert np.array_equal(cs, st.counts) and ps.tolist() == st.past_row(), what
+        assert int(cs.max()) == 0xffffffff and int(cs[_slot(V, order, sec, past[order - sec:], a)]) == 0xffffffff
+        # walk(): the refused step's row is the empty row, and the walk is dead from there on
+        wrows, wst = K.walk(V, order, W, syms, bits, counts, past)
+        assert not wrows[stop:].any() and wrows[:stop].all() and np.array_equal(wst.counts, st.counts)
+        assert wst.past == st.past
+        with pytest.raises(oracle.OracleError) as e:
+            oracle.encode(wrows, syms, 24)
+        assert (e.value.code, e.value.step) == (-5, stop)         # LAC_E_TABLE at that step
+
+
 def test_rules_against_a_sparse_map(cc):
     assert cc.cc_sweep(150, 12345) == 0
 

@@ -6,7 +6,9 @@
 * lac_amd/csrc/lac_fsm.h, the plain host rules the kernels share (tests/native/fsm_check.cpp):
   model limits, prepared-layout offsets, and the prepared row's O(1) {lo, hi, T, ceil(T / minp)}
   and search against a plain scan of 1 000 random rows, totals at 2^32 - 1, 2^50 +- 1, near 2^60 and
-  in [2^63, 2^64) among them; the sweep also runs as a stand-alone ASan + UBSan program.
+  in [2^63, 2^64) among them, and of sparse rows -- at most 8 positive entries at chunk and vector
+  bounds, zero runs of whole chunks -- searched at every c_i - 1, c_i and T - 1; the sweep also
+  runs as a stand-alone ASan + UBSan program.
 """
 import ctypes as C
 import os
