@@ -598,6 +598,52 @@ int lac_count_get_state(lac_ctx *ctx, uint32_t *counts_dev_out, int32_t *past_de
 int lac_count_encode(lac_ctx *ctx, const int32_t *sym_dev, int64_t steps, uint64_t *trace_dev, void *stream);
 int lac_count_decode(lac_ctx *ctx, int64_t steps, int32_t *sym_out_dev, void *stream);
 
+/* ---- match-history models (the reference's History, arith_code.py:364-398) ----
+ * A model that predicts from the longest recent matches: V symbols (the context's), a ring of the
+ * last P in [1, 256] symbols per stream and a table of weights L[i][r] < 2^48 (lag i, run r).
+ * Stream b keeps `ring`, int32 [P], all -1 at the start, and the write index `pasti`, 0 at the
+ * start.  With  p_i = ring[(pasti - 1 - i) mod P]  and  r_i  the number of j = 1, 2, ... < P - i,
+ * taken while they hold, with  ring[(pasti - 1 - i - j) mod P] == ring[(pasti - j) mod P]
+ * (History.runs, :371-380), the table of a step is
+ *   pmf[s] = 1 + sum_{i : p_i == s and p_i > 0} L[i][r_i]      (calc_dist, :381-389, with
+ * lfunc(r, i, n, P) == L[i][r]), and accepting s does ring[pasti] = s, pasti = (pasti + 1) mod P
+ * (accept, :390-393).  The model's quirks are kept: symbol 0, like the -1 filler, never gains
+ * weight (the test is p > 0), and -1 equals -1 in the comparisons, so an empty ring matches
+ * itself.  Step t codes with that row exactly as lac_encode / lac_decode_steps code it -- ceil
+ * mapping, fudged rows included -- so per stream everything (bytes, nbits, registers, decoded
+ * symbols, status codes and err_step) is what the pmf path gives on the rows the ring produces.
+ * One kernel launch per call whatever the steps; the launches report under lac_profile_read's
+ * slots 1 (encode) and 3 (decode_step).
+ *
+ * lac_hist_load  (History.__init__, :365-370) uploads weights_host, uint64 [P][P] with
+ *   L[i * P + r] = lfunc(r, i, V, P), and gives every stream the initial state.  LAC_E_ARG:
+ *   V > 4096, P outside [1, 256], a weight >= 2^48 (so a total stays below 4096 + 256 * 2^48 <
+ *   2^57 and never reaches 2^64), LAC_MAP_FLOOR.  Only between jobs (LAC_E_STATE, lac_fsm_load's
+ *   rule).  A context holds a finite-state, a count and a history model independently; lac_close
+ *   frees all.
+ * lac_hist_set_state / lac_hist_get_state  (:367-368, `past` and `pasti`) every stream's ring
+ *   (int32 [streams][P], device; NULL sets all to -1) and write index (int32 [streams], device;
+ *   NULL: 0), copied on `stream`.  set_state refuses, as a whole and before anything is set, a
+ *   ring entry outside [-1, V) or a pasti outside [0, P) (LAC_E_ARG; it waits for `stream` to
+ *   learn that).  The match lengths the kernels carry from step to step are derived state: they
+ *   are rebuilt from ring and pasti whenever those are set and are no part of what is saved.
+ *   Either output of get_state may be NULL.
+ * lac_hist_encode  (A_to_bin.step with calc_dist + accept, :187-192, :381-393) continues the open
+ *   encode like lac_encode: sym_dev int32 [steps][streams], trace_dev as lac_encode's or NULL.
+ * lac_hist_decode  (A_from_bin.step, :264-299, :381-393) after any lac_decode_open*: sym_out_dev
+ *   int32 [steps][streams] (-1 after an error); honours lac_decode_refill between calls,
+ *   LAC_OPT_DECODE_STOP and lac_decode_determined.
+ * Sticky errors are the pmf path's on the row the ring produces, with its precedence: under a u32
+ * context an entry >= 2^32 is LAC_E_TABLE at that step (u32 rows whose total passes 2^32 are
+ * legal).  A failed step moves neither the ring nor the match lengths.  Both coding calls honour
+ * lac_set_stream_lengths.  Refused before anything is launched: LAC_E_STATE with no history model
+ * loaded, under LAC_MAP_FLOOR or in the wrong mode. */
+int lac_hist_load(lac_ctx *ctx, int P, const uint64_t *weights_host, void *stream);
+int lac_hist_set_state(lac_ctx *ctx, const int32_t *ring_dev, const int32_t *pasti_dev, void *stream);
+int lac_hist_get_state(lac_ctx *ctx, int32_t *ring_dev_out, int32_t *pasti_dev_out, void *stream);
+int lac_hist_encode(lac_ctx *ctx, const int32_t *sym_dev, int64_t steps, uint64_t *trace_dev, void *stream);
+int lac_hist_decode(lac_ctx *ctx, int64_t steps, int32_t *sym_out_dev, void *stream);
+
 /* ---- logits path --------------------------------
  * Tables are computed in-kernel from raw logits with the integer-exact "q1"
  * quantiser instead of being read from a pmf in HBM: for each row

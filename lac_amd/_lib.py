@@ -87,6 +87,11 @@ PROTOTYPES = [
     ("lac_count_get_state", _i, [_vp, _vp, _vp, _vp]),
     ("lac_count_encode", _i, [_vp, _vp, _i64, _vp, _vp]),
     ("lac_count_decode", _i, [_vp, _i64, _vp, _vp]),
+    ("lac_hist_load", _i, [_vp, _i, _vp, _vp]),
+    ("lac_hist_set_state", _i, [_vp, _vp, _vp, _vp]),
+    ("lac_hist_get_state", _i, [_vp, _vp, _vp, _vp]),
+    ("lac_hist_encode", _i, [_vp, _vp, _i64, _vp, _vp]),
+    ("lac_hist_decode", _i, [_vp, _i64, _vp, _vp]),
     ("lac_decode_get_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_set_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_tail_begin", _i, [_vp, _vp]),

@@ -780,6 +780,99 @@ class BatchCoder:
         check(self.lib.lac_count_decode(self.ctx, steps, C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    # ------------------------------------------------------------ match-history models
+    def load_history(self, P, weights):
+        """Load a match-history model (include/lac.h lac_hist_load; the reference's History,
+        arith_code.py:364-398, with lfunc(r, i, n, P) == weights[i][r]): a ring of the last ``P``
+        symbols per stream, all -1, write index 0.  ``weights``: [P, P] non-negative integers
+        below 2^48.  Only between jobs.  1 <= P <= 256, vocab <= 4096."""
+        P = int(P)
+        try:
+            w = np.array([[int(x) for x in row] for row in weights], dtype=object).reshape(max(P, 0), max(P, 0))
+        except (TypeError, ValueError):
+            raise ValueError(f"weights must be [{P}, {P}] integers") from None
+        if any(x < 0 or x >= 1 << 64 for x in w.ravel().tolist()):
+            raise ValueError("weights must be in [0, 2^48)")
+        arr = np.ascontiguousarray(w.astype(np.uint64)) if P > 0 else np.zeros(1, dtype=np.uint64)
+        check(self.lib.lac_hist_load(self.ctx, P, arr.ctypes.data_as(C.c_void_p), self._stream))
+        self.history_past = P
+        self.history_weights = arr
+
+    def _need_history(self):
+        if getattr(self, "history_past", None) is None:
+            from ._lib import LacError, LAC_E_STATE
+            raise LacError(LAC_E_STATE, "no history model: call load_history first")
+
+    def set_history_state(self, ring=None, pasti=None):
+        """Every stream's ring ([streams, P] integers in [-1, vocab), -1 unset; None: all -1) and
+        write index ([streams] integers in [0, P); None: 0).  Copied; the match lengths the
+        kernels keep are rebuilt from them."""
+        torch = _torch()
+        self._need_history()
+        rd = pd = None
+        if ring is not None:
+            arr = ring.detach().cpu().numpy() if isinstance(ring, torch.Tensor) else np.asarray(ring)
+            if arr.size != self.streams * self.history_past:
+                raise ValueError(f"ring must be [{self.streams}, {self.history_past}]")
+            rd = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(self.device)
+        if pasti is not None:
+            arr = pasti.detach().cpu().numpy() if isinstance(pasti, torch.Tensor) else np.asarray(pasti)
+            if arr.size != self.streams:
+                raise ValueError(f"pasti must be [{self.streams}]")
+            pd = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(self.device)
+        check(self.lib.lac_hist_set_state(self.ctx, None if rd is None else C.c_void_p(rd.data_ptr()),
+                                          None if pd is None else C.c_void_p(pd.data_ptr()), self._stream))
+        self._history_keep = (rd, pd)
+
+    def history_state(self):
+        """-> (ring int32 [streams, P], pasti int32 [streams]) as numpy arrays; synchronises."""
+        torch = _torch()
+        self._need_history()
+        ring = torch.empty((self.streams, self.history_past), dtype=torch.int32, device=self.device)
+        pasti = torch.empty((self.streams,), dtype=torch.int32, device=self.device)
+        check(self.lib.lac_hist_get_state(self.ctx, C.c_void_p(ring.data_ptr()), C.c_void_p(pasti.data_ptr()),
+                                          self._stream))
+        return ring.cpu().numpy(), pasti.cpu().numpy()
+
+    def encode_history(self, sym, trace=None):
+        """Continue every stream by ``sym`` [steps, streams] (int32 device tensor) under the
+        loaded history model, in one launch: step t codes with the row the stream's ring gives
+        and then writes the symbol into it.  Bit for bit :meth:`encode` on those rows; ``trace``
+        as there."""
+        torch = _torch()
+        if sym.dtype != torch.int32 or sym.device != self.device:
+            raise TypeError("sym must be an int32 tensor on the coder's device")
+        sym = sym.contiguous()
+        steps = sym.shape[0] if sym.dim() == 2 else 1
+        if sym.numel() != steps * self.streams:
+            raise ValueError(f"sym must be [steps, {self.streams}]")
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int64 or trace.numel() != steps * self.streams * 2 or not trace.is_contiguous():
+                raise ValueError("trace must be a contiguous int64 tensor [steps, streams, 2]")
+            tp = C.c_void_p(trace.data_ptr())
+        self._keep = (sym,)
+        check(self.lib.lac_hist_encode(self.ctx, C.c_void_p(sym.data_ptr()), steps, tp, self._stream))
+
+    def encode_history_job(self, sym):
+        """reset + set_history_state() (empty rings) + encode_history + finish."""
+        self.reset()
+        self.set_history_state()
+        self.encode_history(sym)
+        self.finish()
+
+    def decode_history(self, steps, out=None):
+        """Decode ``steps`` symbols per stream under the loaded history model in one launch (after
+        any decode_open*), from the rings the streams hold.  -> int32 [steps, streams]."""
+        torch = _torch()
+        steps = int(steps)
+        if out is None:
+            out = torch.empty((steps, self.streams), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out(out, steps)
+        check(self.lib.lac_hist_decode(self.ctx, steps, C.c_void_p(out.data_ptr()), self._stream))
+        return out
+
     # ------------------------------------------------------------ logits path
     def _logits_args(self, logits, steps=None):
         """-> (type, step_stride, stream_stride, steps) for a [steps, streams, V]

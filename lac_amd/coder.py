@@ -7,6 +7,8 @@ Drop-in counterparts of /root/reference/arith_code.py:
     CDFPredictor            :76-110  (CDF table; ceil mapping; fudged_dist)
     ProbPredictor           :111-135 (prob / calc_dist / cached dist)
     NFA                     :423-434 (finite-state model: one CDF and one transition row per state)
+    Markov_up_to_n          :443-464 (adaptive n-gram counts)
+    History                 :364-398 (longest recent matches in a ring of past symbols)
     AC                      :144-155 (.to_bin / .from_bin make fresh coders)
     A_to_bin                :156-246 (step, run, bits, encode, flush, __call__)
     A_from_bin              :248-334 (step, run, decode)
@@ -220,6 +222,75 @@ class Markov_up_to_n(ProbPredictor):
         return type(self)(self.n, self.order, self.lfunc, self.past, dict(self.table))   # (a subclass stays one)
 
 
+class MatchWeights:
+    """``lfunc`` of a History given as a table: ``(r, i, n, p) -> table[i][r]`` (i the lag, r the
+    run).  It carries ``table``, which is what lets A_to_bin / A_from_bin hand the model to
+    liblac's match-history kernels (``_history_model``)."""
+
+    def __init__(self, table):
+        self.table = tuple(tuple(int(w) for w in row) for row in table)
+        flat = [w for row in self.table for w in row]
+        self.span = (min(flat), max(flat)) if flat else (0, 0)      # (what _history_model asks of every job)
+        self.shape = (len(self.table), min((len(row) for row in self.table), default=0))
+
+    def __call__(self, r, i, n, p):
+        return self.table[i][r]
+
+
+class History(ProbPredictor):
+    """Match-history predictor (arith_code.py:364-398): ``past`` is a ring of the last
+    ``len(past)`` accepted symbols (-1 unset), ``pasti`` its write index.  For every lag i,
+    ``runs`` yields the symbol p = past[pasti-1-i], i + 1 steps back, with r, the length of the
+    match between what precedes it and what precedes the present -- only for p > 0 -- and
+
+        dist = cumsum(1 + sum_{(p, r, i) in runs(), p == s} lfunc(r, i, n, len(past)))
+
+    ``lfunc=None`` is the reference's default ``n*r**3 + 1`` as a MatchWeights; with a
+    MatchWeights the coders run the model on the device in one launch per job, any other
+    callable is coded per token."""
+
+    def __init__(self, n, past=256, lfunc=None):
+        super().__init__(n)
+        self.past = [-1] * past
+        self.pasti = 0
+        self.n = n
+        self.lfunc = lfunc if lfunc is not None else \
+            MatchWeights([[n * r ** 3 + 1 for r in range(past)] for _ in range(past)])
+
+    def runs(self):
+        P = len(self.past)
+        for i in range(P):
+            p = self.past[self.pasti - 1 - i]
+            r = 0
+            for j in range(1, P - i):
+                if self.past[self.pasti - 1 - i - j] != self.past[self.pasti - j]:
+                    break
+                r += 1
+            if p > 0:
+                yield (p, r, i)
+
+    def calc_dist(self):
+        self.dcache = [1] * self.n
+        for s, r, i in self.runs():
+            self.dcache[s] += self.lfunc(r, i, self.n, len(self.past))
+        p = 0
+        for i in range(len(self.dcache)):
+            p += self.dcache[i]
+            self.dcache[i] = p
+        return self.dcache
+
+    def accept(self, symbol):
+        self.past[self.pasti] = symbol
+        self.pasti = (self.pasti + 1) % len(self.past)
+        return super().accept(symbol)
+
+    def copy(self):
+        h = type(self)(self.n, 0, self.lfunc)                        # (a subclass stays one)
+        h.past = list(self.past)
+        h.pasti = self.pasti
+        return h
+
+
 ternary = Predictor(3)
 
 
@@ -423,6 +494,34 @@ def _count_model(predictor):
     return V, order, tuple(f.weights[:order])
 
 
+def _history_model(predictor):
+    """(V, P, weights) when ``predictor`` is History (arith_code.py:364-398) as liblac's
+    match-history kernels can code it, else None: its ``runs``, ``calc_dist`` and ``accept``
+    resolve to the class's own (a subclass overriding one keeps the per-token path), its mapping
+    is CDFPredictor's, it declares no ``minp`` of its own, its ``lfunc`` is a MatchWeights with a
+    [P, P] table, and the model and its ring are within the kernels' limits (include/lac.h
+    lac_hist_load, lac_hist_set_state)."""
+    for m in ("runs", "calc_dist", "accept"):
+        if _impl(predictor, m) not in ((f"History.{m}", mod) for mod in _REF_MODULES):
+            return None
+    if not _is_table(predictor) or _declared_minp(predictor) is not None:
+        return None
+    f = getattr(predictor, "lfunc", None)
+    try:
+        V, P = int(predictor.n), len(predictor.past)
+        if not isinstance(f, MatchWeights) or not 1 <= P <= 256 or not 1 <= V <= 4096:
+            return None
+        if min(f.shape) < P or f.span[0] < 0 or f.span[1] >= 1 << 48:
+            return None
+        if not isinstance(predictor.past, list) or not 0 <= int(predictor.pasti) < P:
+            return None
+        if any(not -1 <= int(x) < V for x in predictor.past):
+            return None
+    except (TypeError, ValueError, AttributeError):
+        return None
+    return V, P, f
+
+
 class _FsmJob:
     """A finite-state model (``_fsm_model``) as a model the device advances itself: how the
     coders load it, hand over the predictor's state, and code with it."""
@@ -481,12 +580,38 @@ class _CountJob:
         return coder.decode_counts(n)
 
 
+class _HistoryJob:
+    """A match-history model (``_history_model``) as a model the device advances itself.  The
+    predictor object stays the truth: before a job its ring and write index go up, after it the
+    coders replay ``accept`` on it for the symbols coded."""
+
+    def __init__(self, V, P, lfunc):
+        self.V, self.P, self.lfunc = V, P, lfunc
+        self.key = ("history", V, P, id(lfunc))
+
+    def load(self, coder):
+        coder.load_history(self.P, [row[:self.P] for row in self.lfunc.table[:self.P]])
+
+    def begin(self, coder, predictor):
+        coder.set_history_state([[int(x) for x in predictor.past]], [int(predictor.pasti)])
+
+    def encode(self, coder, sym, trace=None):
+        coder.encode_history(sym, trace=trace)
+
+    def decode(self, coder, n):
+        return coder.decode_history(n)
+
+
 def _device_model(predictor, fsm=None):
-    """``predictor`` as a model the device advances itself -- a _CountJob or a _FsmJob -- or
-    None.  ``fsm``: a converted finite-state model to reuse (its conversion reads every table)."""
+    """``predictor`` as a model the device advances itself -- a _CountJob, a _HistoryJob or a
+    _FsmJob -- or None.  ``fsm``: a converted finite-state model to reuse (its conversion reads
+    every table)."""
     cm = _count_model(predictor)
     if cm is not None:
         return _CountJob(*cm)
+    hm = _history_model(predictor)
+    if hm is not None:
+        return _HistoryJob(*hm)
     if fsm is not None:
         return fsm if _fsm_model_still(predictor) else None
     m = _fsm_model(predictor)
@@ -633,7 +758,7 @@ class A_to_bin:
 
     def _model(self):
         """The predictor as a model the device advances (``_device_model``), or None."""
-        if _count_model(self.predictor) is not None:
+        if _count_model(self.predictor) is not None or _history_model(self.predictor) is not None:
             return _device_model(self.predictor)
         t = getattr(self.predictor, "t", None)
         if self._fsm is None or self._fsm[0] is not t:

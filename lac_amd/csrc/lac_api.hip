@@ -104,6 +104,12 @@ int lac_close(lac_ctx *c) {
     (void)hipFree(c->cnt);
     (void)hipFree(c->cnt_past);
     (void)hipFree(c->cnt_row);
+    (void)hipFree((void *)c->hist_L);
+    (void)hipFree(c->hist_ring);
+    (void)hipFree(c->hist_pasti);
+    (void)hipFree(c->hist_M);
+    (void)hipFree(c->hist_row);
+    (void)hipFree(c->hist_flag);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
     return LAC_OK;

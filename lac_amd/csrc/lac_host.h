@@ -11,6 +11,7 @@
 #include "lac_select.h"
 #include "lac_fsm.h"
 #include "lac_count.h"
+#include "lac_history.h"
 
 // ====================================================================== C-ABI
 struct lac_ctx {
@@ -82,13 +83,21 @@ struct lac_ctx {
     bool fsm_has_next = false;
     int32_t *fsm_state = nullptr;       //   [B] every stream's current state, kept across calls
     int *fsm_flag = nullptr;            //   the load's verdict on `next` (an entry outside [0, K))
-    int fsm_busy = 0;                   //   an lac_fsm_decode / lac_count_decode ran since the last lac_decode_open: mid-job
+    int fsm_busy = 0;                   //   an lac_fsm_decode / lac_count_decode / lac_hist_decode ran since the last lac_decode_open: mid-job
     // adaptive count models (lac_count_load, lac_count.hip): every stream's counts (lac_count.h)
     uint32_t *cnt = nullptr;            //   [B][cnt_y.stride]
     int32_t *cnt_past = nullptr;        //   [B][order] the last symbols, most recent last, -1 absent
     void *cnt_row = nullptr;            //   [B][cnt_y.Vc] entries: the row of a step that fudges
     CountLayout cnt_y = {};
     uint32_t cnt_w[4] = {0, 0, 0, 0};
+    // match-history models (lac_hist_load, lac_history.hip): the weights and every stream's ring (lac_history.h)
+    const uint64_t *hist_L = nullptr;   //   [P][P] L[i * P + r], shared by all streams
+    int32_t *hist_ring = nullptr;       //   [B][P] the last P symbols, -1 unset
+    int32_t *hist_pasti = nullptr;      //   [B] the ring's write index
+    int32_t *hist_M = nullptr;          //   [B][P] derived: the match lengths of ring / pasti, rebuilt when they are set
+    void *hist_row = nullptr;           //   [B][4 ceil(V / 4)] entries: the row of a step that fudges
+    int *hist_flag = nullptr;           //   lac_hist_set_state's verdict on the state it was handed
+    int hist_P = 0;
     // live kernel timing (lac_profile_enable): hipEvent pairs around launches
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
