@@ -644,6 +644,62 @@ int lac_hist_get_state(lac_ctx *ctx, int32_t *ring_dev_out, int32_t *pasti_dev_o
 int lac_hist_encode(lac_ctx *ctx, const int32_t *sym_dev, int64_t steps, uint64_t *trace_dev, void *stream);
 int lac_hist_decode(lac_ctx *ctx, int64_t steps, int32_t *sym_out_dev, void *stream);
 
+/* ---- range-level coding (symbol_to_range / val_to_symbol, arith_code.py:94-110) ----
+ * The coder itself needs three integers per symbol: lo = c_{s-1}, hi = c_s and the total T
+ * (symbol_to_range reads dist[s-1], dist[s] and dist[-1] only).  These calls take them instead of
+ * a table, for models whose distribution is a formula (a discretised Gaussian, a uniform law over
+ * 10^12 values) or whose alphabet is too large to write out per step.  Triples are always uint64,
+ * whatever the context's pmf_bits; the context's vocab plays no part.  A triple is valid when
+ * 0 < T <= 2^(prec-1) and lo < hi <= T.  It codes exactly as the table [lo, hi - lo, T - hi] codes
+ * its symbol 1: with T <= 2^(prec-1) no width can fudge (T <= w minp for every w > 2^(prec-1)),
+ * whatever the other two entries are, so per stream everything -- bytes and nbits, lac_enc_state /
+ * lac_dec_state, planes, trace_dev {E, k}, lac_flush_digits, capacity failures with their registers
+ * and what a failed stream freezes -- is what lac_encode / lac_decode_steps give on that table
+ * (lac_amd/csrc/lac_ranges.h).  Totals above 2^(prec-1) are refused: fudging needs the whole table.
+ *
+ * lac_encode_ranges  continues the open encode like lac_encode and mixes with it, the logits calls
+ *   and the model families in one session; lac_set_stream_lengths, lac_encode_drain, _rebase,
+ *   _finish, lac_encode_get_state / _set_state and lac_set_output work around it unchanged.
+ *   lo_dev, hi_dev: [steps][streams]; the total of step t, stream b is
+ *   tot_dev[t * tot_step_stride + b * tot_stream_stride], strides in elements, 0 re-uses the value
+ *   (a per-stream total, or one total for the whole job).  Step t of stream b narrows by
+ *   a = ceil(lo w / T), b = ceil(hi w / T) and renormalises.  Sticky errors, in this precedence:
+ *   LAC_E_TABLE (T = 0, T > 2^(prec-1), hi > T or lo > hi), LAC_E_ZERO_WIDTH (lo == hi),
+ *   LAC_E_CAPACITY (after the narrowing); err_step is the stream's nsym.  One kernel launch per
+ *   call whatever the steps (one lane per stream); it reports under lac_profile_read's slot 1.
+ * lac_encode_ranges_job  reset + lac_encode_ranges + finish (the reset and finish launches are the
+ *   existing ones).
+ * lac_decode_ranges_step  after any lac_decode_open*; one call is "advance by the previous symbol's
+ *   range, then peek the next target", in one launch (slot 3):
+ *   - advance (lo_dev != NULL; lo_dev, hi_dev, tot_dev: [streams]): a live stream with no sticky
+ *     error tests, in order, the triple (LAC_E_TABLE), the registers (x outside [l, h]:
+ *     LAC_E_DECODE_RANGE), lo <= floor((x - l) T / w) < hi (LAC_E_DECODE_RANGE otherwise: the
+ *     range misses the target, as lo == hi always does), then decode_symbol's determined test,
+ *     det = vhi < w && floor(vhi T / w) < hi (with LAC_OPT_DECODE_STOP an undetermined symbol is
+ *     LAC_E_UNDETERMINED; det / ndet count as on the pmf path), then narrows, renormalises, pulls
+ *     bits and counts the symbol.  Where the target lies in [lo, hi) everything equals
+ *     lac_decode_steps on the three-entry table decoding symbol 1.  Every error leaves the stream
+ *     frozen as before the step.
+ *   - peek (next_tot_dev != NULL, [streams]), after the advance: target_out_dev[b] =
+ *     floor((x - l) T' / w), no state changes (twice gives the same values).  UINT64_MAX for a
+ *     stream with a sticky error or at its count, and for a T' that is not valid (the error itself
+ *     is raised by the advance that uses it).
+ *   The caller's model turns targets into symbols and ranges (val_to_symbol) between calls.  The
+ *   call reads the opened buffer like every decode path: lac_decode_open_packed, _open_window,
+ *   lac_decode_refill and lac_set_stream_lengths work between calls.
+ * Refused before anything is launched: LAC_E_STATE under LAC_MAP_FLOOR or LAC_TERM_ACSAMPLER (the
+ * reference's floor-mapped decoder is not an inverse of its encoder) and in the wrong mode
+ * (lac_encode's / lac_decode_steps' rule); LAC_E_ARG for NULL lo / hi / tot on encode, negative
+ * steps or strides, and a decode call with both halves NULL. */
+int lac_encode_ranges(lac_ctx *ctx, const uint64_t *lo_dev, const uint64_t *hi_dev, const uint64_t *tot_dev,
+                      int64_t tot_step_stride, int64_t tot_stream_stride, int64_t steps, uint64_t *trace_dev,
+                      void *stream);
+int lac_encode_ranges_job(lac_ctx *ctx, const uint64_t *lo_dev, const uint64_t *hi_dev, const uint64_t *tot_dev,
+                          int64_t tot_step_stride, int64_t tot_stream_stride, int64_t steps, uint64_t *trace_dev,
+                          void *stream);
+int lac_decode_ranges_step(lac_ctx *ctx, const uint64_t *lo_dev, const uint64_t *hi_dev, const uint64_t *tot_dev,
+                           const uint64_t *next_tot_dev, uint64_t *target_out_dev, void *stream);
+
 /* ---- logits path --------------------------------
  * Tables are computed in-kernel from raw logits with the integer-exact "q1"
  * quantiser instead of being read from a pmf in HBM: for each row

@@ -92,6 +92,9 @@ PROTOTYPES = [
     ("lac_hist_get_state", _i, [_vp, _vp, _vp, _vp]),
     ("lac_hist_encode", _i, [_vp, _vp, _i64, _vp, _vp]),
     ("lac_hist_decode", _i, [_vp, _i64, _vp, _vp]),
+    ("lac_encode_ranges", _i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    ("lac_encode_ranges_job", _i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    ("lac_decode_ranges_step", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("lac_decode_get_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_set_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_tail_begin", _i, [_vp, _vp]),

@@ -873,6 +873,86 @@ class BatchCoder:
         check(self.lib.lac_hist_decode(self.ctx, steps, C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    # ------------------------------------------------------------ range-level coding
+    def _range_tensor(self, x, what, shape):
+        torch = _torch()
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.int64, torch.uint64) or x.device != self.device:
+            raise TypeError(f"{what} must be an int64 (bit pattern of uint64) tensor on the coder's device")
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{what} must be {list(shape)}, got {list(x.shape)}")
+        return x.contiguous()
+
+    def _range_args(self, lo, hi, tot, trace):
+        torch = _torch()
+        if not isinstance(lo, torch.Tensor) or lo.dim() not in (1, 2):
+            raise ValueError(f"lo must be a [steps, {self.streams}] tensor")
+        steps = lo.shape[0] if lo.dim() == 2 else 1
+        shape = (steps, self.streams) if lo.dim() == 2 else (self.streams,)
+        lo, hi = self._range_tensor(lo, "lo", shape), self._range_tensor(hi, "hi", shape)
+        if isinstance(tot, int) and not isinstance(tot, bool):          # one total for the whole job
+            if not 0 <= tot < 1 << 64:
+                raise ValueError("tot must fit uint64")
+            tot = torch.tensor([tot - (1 << 64) if tot >> 63 else tot], dtype=torch.int64, device=self.device)
+            step_stride = stream_stride = 0
+        elif isinstance(tot, torch.Tensor) and tot.dim() == 1 and lo.dim() == 2:   # a total per stream
+            tot = self._range_tensor(tot, "tot", (self.streams,))
+            step_stride, stream_stride = 0, 1
+        else:
+            tot = self._range_tensor(tot, "tot", shape)
+            step_stride, stream_stride = self.streams, 1
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int64 or trace.numel() != steps * self.streams * 2 or not trace.is_contiguous():
+                raise ValueError("trace must be a contiguous int64 tensor [steps, streams, 2]")
+            tp = C.c_void_p(trace.data_ptr())
+        self._keep = (lo, hi, tot)
+        return (self.ctx, C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), C.c_void_p(tot.data_ptr()),
+                step_stride, stream_stride, steps, tp, self._stream)
+
+    def encode_ranges(self, lo, hi, tot, trace=None):
+        """Continue every stream by symbols given as ranges (include/lac.h lac_encode_ranges): step t
+        of stream b narrows by ``lo[t, b] = c_{s-1}``, ``hi[t, b] = c_s`` out of ``tot`` -- what
+        ``symbol_to_range`` reads of a CDF -- with no table anywhere.  ``lo``, ``hi``: int64 device
+        tensors [steps, streams] (bit patterns of uint64); ``tot``: the same shape, [streams] (a
+        total per stream) or a Python int (one total for the job).  Valid: 0 < tot <= 2^(prec-1)
+        and lo < hi <= tot.  Bit for bit :meth:`encode` on the tables [lo, hi - lo, tot - hi] with
+        symbol 1; one launch whatever the steps; ``trace`` as there."""
+        check(self.lib.lac_encode_ranges(*self._range_args(lo, hi, tot, trace)))
+
+    def encode_ranges_job(self, lo, hi, tot, trace=None):
+        """reset + :meth:`encode_ranges` + finish."""
+        check(self.lib.lac_encode_ranges_job(*self._range_args(lo, hi, tot, trace)))
+
+    def decode_ranges_step(self, prev=None, next_tot=None, out=None):
+        """One position of a range-level decode (include/lac.h lac_decode_ranges_step), one launch:
+        advance every stream by ``prev = (lo, hi, tot)``, the range of the symbol its last target
+        named (int64 device tensors [streams]; None: no advance), then peek the next targets under
+        the totals ``next_tot`` ([streams] or a Python int; None: no peek).  -> int64 [streams]
+        targets ``floor((x - l) * T' / w)`` (``out`` or a new tensor; -1, the bit pattern of
+        UINT64_MAX, for a stream with a sticky error, at its count, or with an invalid total), or
+        None without a peek.  The caller's model maps a target to its symbol and range."""
+        torch = _torch()
+        lo = hi = tot = None
+        if prev is not None:
+            lo, hi, tot = (self._range_tensor(x, n, (self.streams,)) for x, n in zip(prev, ("lo", "hi", "tot")))
+        nt = None
+        if next_tot is not None:
+            if isinstance(next_tot, int) and not isinstance(next_tot, bool):
+                nt = torch.full((self.streams,), next_tot - (1 << 64) if next_tot >> 63 else next_tot,
+                                dtype=torch.int64, device=self.device)
+            else:
+                nt = self._range_tensor(next_tot, "next_tot", (self.streams,))
+            if out is None:
+                out = torch.empty((self.streams,), dtype=torch.int64, device=self.device)
+            elif out.dtype != torch.int64 or out.device != self.device or tuple(out.shape) != (self.streams,) \
+                    or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int64 [{self.streams}] tensor on the coder's device")
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        self._keep = (lo, hi, tot, nt)
+        check(self.lib.lac_decode_ranges_step(self.ctx, p(lo), p(hi), p(tot), p(nt), p(out) if nt is not None else None,
+                                              self._stream))
+        return out if nt is not None else None
+
     # ------------------------------------------------------------ logits path
     def _logits_args(self, logits, steps=None):
         """-> (type, step_stride, stream_stride, steps) for a [steps, streams, V]
