@@ -700,6 +700,58 @@ int lac_encode_ranges_job(lac_ctx *ctx, const uint64_t *lo_dev, const uint64_t *
 int lac_decode_ranges_step(lac_ctx *ctx, const uint64_t *lo_dev, const uint64_t *hi_dev, const uint64_t *tot_dev,
                            const uint64_t *next_tot_dev, uint64_t *target_out_dev, void *stream);
 
+/* ---- sparse rows: top-k pairs over a uniform floor ----
+ * A row given as at most K (symbol, weight) pairs plus one integer: the form top-k logprob outputs,
+ * truncated samplers and the match model's rows have.  A call names a base weight `base` (>= 1, one
+ * per call), a slot count K (a multiple of 4, 4 <= K <= 256) and two device arrays, idx (int32) and
+ * wt (uint32); row (t, b) is the K slots at element t * step_stride + b * stream_stride of both
+ * (strides in slots; a step stride of 0 re-uses the rows, as in lac_encode).  With n the number of
+ * leading slots with idx >= 0 the row stands for the dense table over the context's vocab V
+ *     pmf[s] = base + (wt_j if s == idx_j for some j < n, else 0),   T = base V + sum_{j<n} wt_j
+ * A row is valid when every pair has idx_j in [0, V), the pairs are strictly ascending in idx, every
+ * slot j >= n has idx == -1 (its weight is ignored) and T <= 2^(prec-1); wt_j = 0 is legal.  Any
+ * other row -- a pair after a pad, an equal or descending index, an idx < -1 or >= V, a total that
+ * is too large -- is LAC_E_TABLE for the stream whose step reaches it.  As with ranges, totals above
+ * 2^(prec-1) are refused rather than fudged: every entry is at least 1, so T <= 2^(prec-1) < w minp
+ * at every coder state and no row can fudge.
+ *
+ * Equivalence, which is the contract: per stream a valid sparse row codes exactly as
+ * lac_encode_ranges / lac_decode_ranges_step code the triple of the dense row, which is what a
+ * pmf_bits = 64 context's lac_encode / lac_decode_steps give on the dense row -- bytes and nbits,
+ * lac_enc_state / lac_dec_state, planes and trace_dev {E, k}, lac_flush_digits, decoded symbols and
+ * det / ndet, capacity failures with their registers, and what a failed stream freezes.  The
+ * context's own pmf_bits plays no part.  The rules, as whole-row rules and as the per-lane
+ * partials the kernels run, are lac_amd/csrc/lac_sparse.h.
+ *
+ * lac_encode_sparse  continues the open encode like lac_encode and mixes with it, the logits calls,
+ *   the ranges calls and the model families in one session; sym_dev: [steps][streams].  For symbol
+ *   s: lo = base s + sum_{idx_j < s} wt_j, hi = lo + base + sum_{idx_j == s} wt_j, then the range
+ *   step.  Sticky errors, in this precedence: LAC_E_SYMBOL_RANGE (s not in [0, V)), LAC_E_TABLE
+ *   (the row), LAC_E_CAPACITY (after the narrowing); zero width cannot occur.  One wave per stream,
+ *   one kernel launch per call whatever the steps (lac_profile_read's slot 1); streams ended by
+ *   lac_set_stream_lengths fetch nothing.
+ * lac_encode_sparse_job  reset + lac_encode_sparse + finish (the existing reset and finish launches).
+ * lac_decode_sparse_steps  after any lac_decode_open*; one launch (slot 3) for `steps` positions.
+ *   A step computes the target t = floor((x - l) T / w) and finds its symbol among the pairs and the
+ *   plain entries between them (a wave scan of the weights, no walk over V), then runs the range
+ *   decode frame: registers test, determined test with LAC_OPT_DECODE_STOP, narrow, renormalise,
+ *   pull.  Errors: the row first (LAC_E_TABLE), then the registers (LAC_E_DECODE_RANGE), then
+ *   LAC_E_UNDETERMINED.  sym_out_dev: [steps][streams], -1 where a stream decoded nothing.  The
+ *   opened buffer is read like on every decode path: lac_decode_open_packed, _open_window,
+ *   lac_decode_refill, lac_decode_determined and lac_set_stream_lengths work around it unchanged.
+ * Refused before anything is launched: LAC_E_STATE under LAC_MAP_FLOOR or LAC_TERM_ACSAMPLER and in
+ * the wrong mode (lac_encode's / lac_decode_steps' rule); LAC_E_ARG for K not a multiple of 4 in
+ * [4, 256], base = 0, a stride that is negative or no multiple of 4, an array that is NULL or not
+ * 16-byte aligned, negative steps, and a NULL sym_dev / sym_out_dev with steps > 0. */
+int lac_encode_sparse(lac_ctx *ctx, const int32_t *idx_dev, const uint32_t *wt_dev, int K, int64_t step_stride,
+                      int64_t stream_stride, uint32_t base, const int32_t *sym_dev, int64_t steps,
+                      uint64_t *trace_dev, void *stream);
+int lac_encode_sparse_job(lac_ctx *ctx, const int32_t *idx_dev, const uint32_t *wt_dev, int K, int64_t step_stride,
+                          int64_t stream_stride, uint32_t base, const int32_t *sym_dev, int64_t steps,
+                          uint64_t *trace_dev, void *stream);
+int lac_decode_sparse_steps(lac_ctx *ctx, const int32_t *idx_dev, const uint32_t *wt_dev, int K, int64_t step_stride,
+                            int64_t stream_stride, uint32_t base, int64_t steps, int32_t *sym_out_dev, void *stream);
+
 /* ---- logits path --------------------------------
  * Tables are computed in-kernel from raw logits with the integer-exact "q1"
  * quantiser instead of being read from a pmf in HBM: for each row

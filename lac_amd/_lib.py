@@ -95,6 +95,9 @@ PROTOTYPES = [
     ("lac_encode_ranges", _i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     ("lac_encode_ranges_job", _i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     ("lac_decode_ranges_step", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lac_encode_sparse", _i, [_vp, _vp, _vp, _i, _i64, _i64, C.c_uint32, _vp, _i64, _vp, _vp]),
+    ("lac_encode_sparse_job", _i, [_vp, _vp, _vp, _i, _i64, _i64, C.c_uint32, _vp, _i64, _vp, _vp]),
+    ("lac_decode_sparse_steps", _i, [_vp, _vp, _vp, _i, _i64, _i64, C.c_uint32, _i64, _vp, _vp]),
     ("lac_decode_get_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_set_state", _i, [_vp, _vp, _vp]),
     ("lac_decode_tail_begin", _i, [_vp, _vp]),

@@ -953,6 +953,92 @@ class BatchCoder:
                                               self._stream))
         return out if nt is not None else None
 
+    # ------------------------------------------------------------ sparse rows
+    def _sparse_rows(self, idx, wt, base, steps=None):
+        """-> (idx, wt, K, step_stride, stream_stride, base, steps) of a [steps, streams or 1, K] or
+        [streams or 1, K] pair of tensors; strides (in slots) are taken from idx, and wt is brought
+        to the same layout as uint32 bit patterns."""
+        torch = _torch()
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.device != self.device:
+            raise TypeError("idx must be an int32 tensor on the coder's device")
+        if not isinstance(wt, torch.Tensor) or wt.dtype not in (torch.int32, torch.int64) or wt.device != self.device:
+            raise TypeError("wt must be an int64 or int32 (bit pattern of uint32) tensor on the coder's device")
+        if idx.shape != wt.shape:
+            raise ValueError(f"idx is {list(idx.shape)}, wt is {list(wt.shape)}")
+        if isinstance(base, bool) or not isinstance(base, int) or not 0 <= base < 1 << 32:
+            raise ValueError("base must be a Python int that fits uint32")
+        if idx.dim() == 2:
+            if steps not in (None, 1):
+                raise ValueError("a 2-D idx is [streams or 1, K] for one step")
+            idx, wt = idx.unsqueeze(0), wt.unsqueeze(0)
+        if idx.dim() != 3 or idx.shape[1] not in (1, self.streams) or (steps is not None and idx.shape[0] not in (1, steps)):
+            raise ValueError(f"idx must be [steps, {self.streams} or 1, K], got {list(idx.shape)}")
+        if idx.stride(-1) != 1:
+            raise ValueError("the K slots of a row must be contiguous")
+        if wt.dtype != torch.int32 or wt.stride() != idx.stride() or wt.data_ptr() % 16:
+            # one copy of the rows idx really holds (its expanded dims re-use theirs), laid out as idx's
+            core = tuple(slice(0, 1) if st == 0 and n > 1 else slice(None) for st, n in zip(idx.stride(), idx.shape))
+            ci, cw = idx[core], wt[core]
+            if cw.dtype == torch.int64:                          # uint32 values held in int64 -> their bit patterns
+                if bool(((cw < 0) | (cw >= 1 << 32)).any()):     # (synchronises; int32 weights are taken as they are)
+                    raise ValueError("an int64 weight outside [0, 2^32)")
+                cw = torch.where(cw >= 1 << 31, cw - (1 << 32), cw)
+            buf = torch.empty_strided(ci.shape, ci.stride(), dtype=torch.int32, device=self.device)
+            buf.copy_(cw)
+            wt = buf.expand(idx.shape)
+        steps = idx.shape[0] if steps is None else steps
+        step_stride = idx.stride(0) if idx.shape[0] > 1 else 0
+        stream_stride = idx.stride(1) if idx.shape[1] > 1 else 0
+        return idx, wt, idx.shape[2], step_stride, stream_stride, base, steps
+
+    def _sparse_encode_args(self, idx, wt, base, sym, trace):
+        torch = _torch()
+        if sym.dtype != torch.int32 or sym.device != self.device:
+            raise TypeError("sym must be an int32 tensor on the coder's device")
+        sym = sym.contiguous()
+        steps = sym.shape[0] if sym.dim() == 2 else 1
+        if sym.numel() != steps * self.streams:
+            raise ValueError(f"sym must be [steps, {self.streams}]")
+        idx, wt, K, step_stride, stream_stride, base, steps = self._sparse_rows(idx, wt, base, steps)
+        tp = None
+        if trace is not None:
+            if trace.dtype != torch.int64 or trace.numel() != steps * self.streams * 2 or not trace.is_contiguous():
+                raise ValueError("trace must be a contiguous int64 tensor [steps, streams, 2]")
+            tp = C.c_void_p(trace.data_ptr())
+        self._keep = (idx, wt, sym)
+        return (self.ctx, C.c_void_p(idx.data_ptr()), C.c_void_p(wt.data_ptr()), K, step_stride, stream_stride, base,
+                C.c_void_p(sym.data_ptr()), steps, tp, self._stream)
+
+    def encode_sparse(self, idx, wt, base, sym, trace=None):
+        """Continue every stream by ``sym[t, b]`` under sparse rows (include/lac.h lac_encode_sparse):
+        row (t, b) is the K slots ``idx[t, b, :]`` (int32: ascending symbols, then -1 pads) with the
+        weights ``wt[t, b, :]`` (int64 in [0, 2^32), checked, or int32 bit patterns of uint32) over the floor ``base`` -- the
+        dense row ``base + wt_j at idx_j``.  ``idx``, ``wt``: [steps, streams or 1, K] or
+        [streams or 1, K] (one step), K a multiple of 4 in [4, 256]; ``expand``-ed dims re-use rows,
+        strides are taken from ``idx`` (multiples of 4, rows 16-byte aligned).  Bit for bit
+        :meth:`encode` of a ``pmf_bits = 64`` coder on ``lac_amd.sparse.dense_rows``; one launch
+        whatever the steps; ``trace`` as there."""
+        check(self.lib.lac_encode_sparse(*self._sparse_encode_args(idx, wt, base, sym, trace)))
+
+    def encode_sparse_job(self, idx, wt, base, sym, trace=None):
+        """reset + :meth:`encode_sparse` + finish."""
+        check(self.lib.lac_encode_sparse_job(*self._sparse_encode_args(idx, wt, base, sym, trace)))
+
+    def decode_sparse(self, idx, wt, base, out=None):
+        """Decode one symbol per stream per step under sparse rows (include/lac.h
+        lac_decode_sparse_steps); rows as in :meth:`encode_sparse`.  -> int32 [steps, streams]."""
+        torch = _torch()
+        idx, wt, K, step_stride, stream_stride, base, steps = self._sparse_rows(idx, wt, base)
+        if out is None:
+            out = torch.empty((steps, self.streams), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out(out, steps)
+        self._keep = (idx, wt)
+        check(self.lib.lac_decode_sparse_steps(self.ctx, C.c_void_p(idx.data_ptr()), C.c_void_p(wt.data_ptr()), K,
+                                               step_stride, stream_stride, base, steps, C.c_void_p(out.data_ptr()),
+                                               self._stream))
+        return out
+
     # ------------------------------------------------------------ logits path
     def _logits_args(self, logits, steps=None):
         """-> (type, step_stride, stream_stride, steps) for a [steps, streams, V]
