@@ -12,6 +12,11 @@
   set_state; the sweep also runs as a stand-alone ASan + UBSan program.
 * coder.History and coder.MatchWeights against the restatement, and on the per-token path's
   yardstick with a lambda ``lfunc``.
+* The jobs of tests/test_gpu_history_limits.py (builders in tests/history.py): each reaches, on
+  the restatement and the C oracle, what it is built to reach -- the weight limit and its totals,
+  the shares of fudged steps, totals next to 2^50, u32 entries of 2^32 - 1 and 2^32, weights that
+  tell the lags on two sides of a lane seam apart, every seam position of the decoder's search
+  coded, and probes that sit exactly on a symbol's range bounds.
 """
 import ctypes as C
 import os
@@ -276,3 +281,146 @@ def test_history_class_is_the_issues_model():
     bad = History(V, P)
     bad.past[1] = V
     assert _history_model(bad) is None                                              # a ring entry outside [-1, V)
+
+
+# ------------------------------------------------------------------ the jobs of test_gpu_history_limits.py
+# Each job reaches, on the host restatement and the C oracle, what it is built to reach.
+WIDE_SHAPES = ((300, 4), (300, 256), (4096, 65))
+WIDE_PRECS = (61, 57, 50, 48, 16)
+SEAM_P = (127, 128, 129, 191, 192, 193, 255)
+STEER_V = {32: (255, 256, 513, 4093, 4096), 64: (127, 128, 257, 4096)}
+PROBES = ((32, 513, 48), (32, 513, 16), (64, 257, 60), (64, 257, 16))   # (entry bits, V, prec): prec 16 fudges
+
+
+def test_wide_weights_are_the_issues_table():
+    for P in (4, 65, 256):
+        L = H.wide_weights(P)
+        assert all(L[i][P - i - 1] == H.W48 for i in range(P)) and max(map(max, L)) == H.W48
+        assert {0, 1, (1 << 32) - 1, 1 << 32} <= {x for r in L for x in r}
+        pick = lambda i, r: (0, 1, (1 << 32) - 1, 1 << 32, (1 << 47) + i, H.W48 - r)[(7 * i + 3 * r) % 6]  # noqa: E731
+        assert all(L[i][r] == pick(i, r) for i in range(P) for r in range(P) if r != P - i - 1)
+
+
+@pytest.mark.parametrize("V,P", WIDE_SHAPES)
+def test_wide_jobs_code_cleanly_and_reach_the_weight_limit(V, P):
+    _, _, L, bits, sym, rows, _ = H.job("wide", V, P)
+    assert sym.shape == (2 * P + 9, 5) and bits == 64
+    for prec in WIDE_PRECS + (51,):
+        assert not H.job_verdict(prec, "wide", V, P)["code"].any(), prec
+    tot = H.totals(rows)
+    assert int(tot.max()) == V + P * H.W48                          # the constant streams reach the documented maximum
+    if (V, P) == (300, 256):
+        assert int(tot.max()) == (1 << 56) + 44
+
+
+def test_wide_job_fudge_classes():
+    tot = H.totals(H.job("wide", 300, 256)[5])
+    always, some, never = H.fudge_classes(tot, 61)
+    assert never == 1.0
+    always, some, never = H.fudge_classes(tot, 57)                  # measured: 0 / 10.3 % / 89.7 %
+    assert always == 0 and some >= 0.05
+    for prec in (48, 16):                                           # measured at 48: 79.2 % / 0.2 % / 20.6 %
+        always, some, never = H.fudge_classes(tot, prec)
+        assert always >= 0.5 and never >= 0.1, prec
+
+
+def test_wide_job_totals_near_2_50():
+    """(300, 4): at prec 50 a total <= 2^49 never fudges and takes the decoder's small division
+    form with a large T; prec 51 takes the general form on the same rows.  Measured: 24 and 13 of
+    85 steps."""
+    tot = [int(x) for x in H.totals(H.job("wide", 300, 4)[5]).reshape(-1)]
+    assert len(tot) == 85
+    assert sum((1 << 47) <= x <= (1 << 49) for x in tot) >= 10
+    assert sum((1 << 49) < x < (1 << 50) for x in tot) >= 10
+
+
+def test_u32_edge_job_sits_on_the_last_entry_that_fits():
+    V, P, L, _, sym, rows, sts = H.job("edge32", 32, 0, 64, 128)
+    r64 = H.job("edge32", 64, 0, 64, 128)[5]
+    top = r64.max(axis=2)
+    assert [int(top[t, 0]) for t in (63, 64, 65, 128, 129)] == [1 << 31, 1 << 31, (1 << 32) - 1, (1 << 32) - 1, 1 << 32]
+    assert (top[65:129, 0] == (1 << 32) - 1).all() and not rows[129:, 0].any() and rows[128, 0].any()
+    coded = r64[np.arange(140), 1, sym[:, 1]]
+    assert int((coded == (1 << 32) - 1).sum()) == 35 and int(top[:, 1].max()) == (1 << 32) - 1
+    for prec in (48, 16):
+        v = H.job_verdict(prec, "edge32", 32, 0, 64, 128)
+        assert v["code"].tolist() == [-5, 0, -5, 0] and v["step"].tolist() == [129, -1, 129, -1]    # LAC_E_TABLE
+        assert not H.job_verdict(prec, "edge32_clean", 64, 0, 64, 128)["code"].any()
+    assert sts[0].pasti == sts[2].pasti == 129 and sts[0].ring == [5] * 129 + [-1] * 63
+    # the same entries from the lags of three lanes
+    rows2 = H.job("edge32_lanes", 32)[5]
+    v = H.job_verdict(48, "edge32_lanes", 32)
+    assert v["code"].tolist() == [-5, 0] and v["step"].tolist() == [3, -1]
+    assert [int(rows2[t, 0].max()) for t in range(4)] == [1, 1 << 31, (1 << 32) - 1, 0]
+
+
+def _bytes_change(P, L):
+    V, _, _, _, sym, _, _ = H.job("seam", P)
+    rows, _ = H.walk_batch(V, P, L, sym, 32)
+    import errors
+    import types
+    v = errors.verdict(types.SimpleNamespace(B=3, prec=48), rows, sym)
+    return [b for b in range(3) if v["data"][b] != H.job_verdict(48, "seam", P)["data"][b]]
+
+
+@pytest.mark.parametrize("P", SEAM_P)
+def test_lag_seam_jobs_tell_the_lags_apart(P):
+    """The oracle's bytes change when the weight rows on two sides of a lane seam change places,
+    and when the last lag loses its weights (measured: streams 1 and 2, for every P)."""
+    L = H.job("seam", P)[2]
+    assert not H.job_verdict(48, "seam", P)["code"].any()
+    for a in (63, 127, 191):
+        if a + 1 < P:
+            M = [r[:] for r in L]
+            M[a], M[a + 1] = M[a + 1], M[a]
+            assert _bytes_change(P, M), a
+    M = [r[:] for r in L]
+    M[P - 1] = [0] * P
+    assert _bytes_change(P, M)
+
+
+@pytest.mark.parametrize("bits,V", [(b, V) for b in (32, 64) for V in STEER_V[b]])
+def test_steered_jobs_code_every_seam_position(bits, V):
+    """Every seam position is coded with the entry 1 (P = 4: never in the ring) and -- but for
+    symbol 0, whose entry is 1 by the model's rule -- with an entry above 1 (P = 64)."""
+    S = H.seam_positions(V, bits)
+    assert len(S) > 4 and {0, 1, V - 2, V - 1} <= set(S)
+    seen = {}
+    for P in (4, 64):
+        _, _, _, _, sym, rows, _ = H.job("steered", V, bits, P)
+        assert sym[:len(S), 0].tolist() == S and sym[:len(S), 1].tolist() == S[::-1]
+        e = rows[np.arange(len(sym))[:, None], np.arange(2)[None, :], sym]
+        seen[P] = ({int(s) for s in sym[e == 1]}, {int(s) for s in sym[e > 1]})
+        assert not H.job_verdict(48, "steered", V, bits, P)["code"].any()
+        assert H.fudge_classes(H.totals(rows), 48)[2] == 1.0          # prec 48: never fudged
+    assert seen[4] == (set(S), set()) and seen[64][1] == set(S) - {0}
+    if V == 4096:
+        assert not H.job_verdict(16, "steered", V, bits, 64)["code"].any()
+        assert H.fudge_classes(H.totals(H.job("steered", V, bits, 64)[5]), 16)[0] > 0.5
+
+
+def probe_model(bits, V, prec):
+    """The exact-bounds probes' weights, ring, row and (s, x) pairs."""
+    L = H.seam_weights(16, (1 << 20) if prec == 16 else 0)
+    ring, pasti = H.probe_ring(V, bits)
+    row = H.Stream(V, 16, L, ring, pasti).row()
+    return L, ring, pasti, row, H.bound_probes(row, V, bits, prec)
+
+
+@pytest.mark.parametrize("bits,V,prec", PROBES)
+def test_bound_probes_sit_on_the_cdf_bounds(bits, V, prec):
+    from oracle import restate
+    L, ring, pasti, row, probes = probe_model(bits, V, prec)
+    cdf, w = restate.cdf_of(row), 1 << prec
+    assert len(probes) == {(32, 48): 24, (32, 16): 19, (64, 60): 20, (64, 16): 16}[bits, prec]
+    assert (cdf[-1] > w) == (prec == 16)                             # fudged at prec 16 alone
+    assert {s for s, _ in probes} >= set(H.seam_positions(V, bits))
+    for s, x in probes:
+        a, b = restate.symbol_to_range(cdf, 1, s, w)
+        assert x in (a, b - 1) and restate.val_to_symbol(cdf, 1, x, w) == s
+        if s > 0:
+            assert restate.val_to_symbol(cdf, 1, a - 1, w) == s - 1
+        if s + 1 < V:
+            assert restate.val_to_symbol(cdf, 1, b, w) == s + 1
+        if prec != 16:                                              # w >= T: the targets are c_{s-1} and c_s - 1
+            assert a * cdf[-1] // w == (cdf[s - 1] if s else 0) and (b - 1) * cdf[-1] // w == cdf[s] - 1
