@@ -139,13 +139,18 @@ enum {                       /* lac_set_option */
                                       on over zero padding; decodes then take the STATS path.  0 =
                                       off (default).  For decoders that stop where the reference's
                                       run(bits, stop=0) stops (lac_amd.coder.A_from_bin) */
-    LAC_OPT_Q1_STEP = 10           /* lac_decode_logits_step / lac_encode_logits_step: 0 = auto (default):
+    LAC_OPT_Q1_STEP = 10,          /* lac_decode_logits_step / lac_encode_logits_step: 0 = auto (default):
                                       the fused one-launch step where it holds the job -- rows of
                                       <= 16384 vectors (bf16 vocab <= 131072, f32 <= 65536) and few
                                       enough streams --, else the two launches of the `steps = 1`
                                       calls; 1 = fused (a shape it cannot take: LAC_E_ARG from the step
                                       call, nothing launched, no state changed); 2 = the two-launch
                                       path.  Identical results, only speed differs */
+    LAC_OPT_TOPK_FORM = 11         /* lac_topk_logits: 0 = auto (default): the registers form where a row is
+                                      <= 16384 vectors (bf16 vocab <= 131072, f32 <= 65536), else the
+                                      streamed form; 1 = registers (a longer row: LAC_E_ARG from the call,
+                                      nothing launched or written); 2 = streamed (any row).  Identical
+                                      results, only speed differs */
 };
 enum {
     LAC_MAP_CEIL = 0,              /* CDFPredictor.symbol_to_range + fudged_dist (arith_code.py:83-110) */
@@ -825,6 +830,41 @@ int lac_q1_group_aborted(lac_ctx *ctx, int64_t *aborted, void *stream);
 /* Materialise the q1 tables: pmf_out_dev[(t*streams + b)*vocab + i] (uint32). */
 int lac_quantize_logits(lac_ctx *ctx, const void *logits_dev, int logit_type, int64_t step_stride,
                         int64_t stream_stride, int64_t steps, uint32_t *pmf_out_dev, void *stream);
+
+/* ---- top-k rows straight from logits -------------------------------------
+ * One kernel reads each logits row once and writes its sparse form -- the rows lac_encode_sparse /
+ * lac_decode_sparse_steps take -- by an integer-exact rule both sides of a codec reproduce (the
+ * rules in both of their forms: lac_amd/csrc/lac_topk.h).  For one row x[0..V), bf16 or f32 with
+ * the logits path's layout rules above:
+ *   1. weights    g_i = TAB[544 - j_i] with j_i exactly q1's level (m, c and j_i as above): the q1
+ *                 table at k = 24 whatever the context's prec -- what lac_quantize_logits writes on
+ *                 a context whose lac_q1_k is 24.
+ *   2. selection  the k entries largest by g survive; among equal g the lower symbol wins.  The key
+ *                 is g, not j: TAB has 453 distinct values over its 545 levels (the first equal
+ *                 pair is TAB[423] = TAB[424] = 30), so adjacent levels can form one tie class.
+ *                 Flat rows, all -inf rows and rows containing +inf are all-tie rows: symbols
+ *                 0..k-1.
+ *   3. output     K slots, K a multiple of 4 with k <= K <= 256.  Slots 0..k-1: the survivors in
+ *                 ascending symbol order, idx_j (int32) and wt_j = g >> (24 - weight_bits) (uint32,
+ *                 may be 0).  Slots k..K-1: idx -1, wt 0.  A valid lac_encode_sparse row by
+ *                 construction (base >= 1 is the caller's, as is T <= 2^(prec-1):
+ *                 base V + k 2^weight_bits bounds it).
+ * Row (t, b) is read at logits_dev + t*step_stride + b*stream_stride (elements) and written at
+ * element (t*streams + b)*K of idx_out_dev and wt_out_dev (contiguous).  Like lac_quantize_logits
+ * the call touches no stream state, works in any mode, mapping and termination, has no sticky
+ * errors and computes every row (lac_set_stream_lengths is ignored).  One launch whatever the
+ * steps, one workgroup per row (LAC_OPT_TOPK_FORM); it reports under lac_profile_read's slot 6.
+ * LAC_E_ARG before anything is launched or written: a bad logit type, negative steps or strides,
+ * k outside [1, min(V, 256)], K not a multiple of 4 or outside [k, 256], weight_bits outside
+ * [0, 24]; with steps > 0 also NULL arrays, a logits layout the logits path refuses, outputs not
+ * 16-byte aligned, a forced form that cannot hold the row, steps x streams >= 2^31.  steps == 0
+ * is LAC_OK with no launch.
+ * lac_topk_form: the form (1 registers, 2 streamed) the next such call runs for this logit type. */
+int lac_topk_logits(lac_ctx *ctx, const void *logits_dev, int logit_type, int64_t step_stride, int64_t stream_stride,
+                    int64_t steps, int k, int weight_bits, int K,
+                    int32_t *idx_out_dev, uint32_t *wt_out_dev, /* [steps][streams][K], contiguous */
+                    void *stream);
+int lac_topk_form(lac_ctx *ctx, int logit_type);
 
 /* Synchronise; ndet_host[streams] = how many leading decoded symbols the
  * available bits determine, i.e. how many symbols the reference's bit-serial

@@ -117,6 +117,8 @@ PROTOTYPES = [
     ("lac_quantize_logits", _i, [_vp, _vp, _i, _i64, _i64, _i64, _vp, _vp]),
     ("lac_decode_logits_step", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
     ("lac_encode_logits_step", _i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    ("lac_topk_logits", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    ("lac_topk_form", _i, [_vp, _i]),
 ]
 
 KERNEL_IDS = {"row_stats": 0, "encode": 1, "finish": 2, "decode_step": 3, "encode_fused": 4, "decode_wave": 5,
@@ -134,6 +136,8 @@ LAC_OPT_BLOCK_WAVES = 8
 LAC_OPT_DECODE_STOP = 9
 LAC_OPT_Q1_STEP = 10
 Q1_STEP_MODES = {"auto": 0, "fused": 1, "split": 2}
+LAC_OPT_TOPK_FORM = 11
+TOPK_FORMS = {"auto": 0, "registers": 1, "streamed": 2}
 LAC_MAP_CEIL, LAC_MAP_FLOOR = 0, 1
 LAC_TERM_FLUSH, LAC_TERM_ACSAMPLER = 0, 1
 LAC_TAIL_DECIDE, LAC_TAIL_FLUSH = 0, 1

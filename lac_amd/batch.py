@@ -1149,6 +1149,53 @@ class BatchCoder:
                                            C.c_void_p(out.data_ptr()), self._stream))
         return out
 
+    # ------------------------------------------------------------ top-k rows from logits
+    def topk_logits(self, logits, k, weight_bits=24, K=None, out=None):
+        """The sparse rows of logits in one launch (include/lac.h lac_topk_logits): per row the k
+        heaviest q1 entries -- weights ``TAB[544 - level]``, the lower symbol first among equal
+        weights -- in ascending symbol order with ``wt = g >> (24 - weight_bits)``, then pads
+        (idx -1, wt 0) up to ``K`` slots (default: k rounded up to a multiple of 4).  ``logits``
+        [steps, streams or 1, V] or [streams or 1, V], bf16 / f32, laid out as the logits path takes
+        them.  -> (idx int32, wt int32 bit patterns of uint32), both [steps, streams, K]: what
+        :meth:`encode_sparse` / :meth:`decode_sparse` take without conversion.  ``out``: such a
+        pair to write into.  Touches no stream state; integer-exact, so both sides of a codec get
+        identical rows from identical logits."""
+        torch = _torch()
+        typ, ss, bs, steps, logits = self._logits_args(logits)
+        k = int(k)
+        K = (k + 3) // 4 * 4 if K is None else int(K)
+        shape = (steps, self.streams, K)
+        if out is None:
+            idx = torch.empty(shape, dtype=torch.int32, device=self.device)
+            wt = torch.empty(shape, dtype=torch.int32, device=self.device)
+        else:
+            idx, wt = out
+            for t in (idx, wt):
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device
+                        or tuple(t.shape) != shape or not t.is_contiguous()):
+                    raise ValueError(f"out must be two contiguous int32 tensors {list(shape)} on the coder's device")
+        self._keep = (logits, idx, wt)
+        check(self.lib.lac_topk_logits(self.ctx, C.c_void_p(logits.data_ptr()), typ, ss, bs, steps, k, int(weight_bits),
+                                       K, C.c_void_p(idx.data_ptr()), C.c_void_p(wt.data_ptr()), self._stream))
+        return idx, wt
+
+    def set_topk_form(self, form):
+        """Which kernel form :meth:`topk_logits` runs (include/lac.h LAC_OPT_TOPK_FORM; identical
+        results): "auto" (0) the registers form where a row is at most 16384 16-byte vectors, else
+        the streamed form; "registers" (1) always -- a longer row raises LacError (LAC_E_ARG) from
+        the call --; "streamed" (2) always."""
+        v = _lib.TOPK_FORMS.get(form, form)
+        check(self.lib.lac_set_option(self.ctx, _lib.LAC_OPT_TOPK_FORM, int(v)))
+
+    def topk_form(self, dtype):
+        """The form (1 registers, 2 streamed) :meth:`topk_logits` runs for logits of ``dtype``."""
+        torch = _torch()
+        typ = {torch.bfloat16: _lib.LAC_LOGITS_BF16, torch.float32: _lib.LAC_LOGITS_F32}[dtype]
+        rc = self.lib.lac_topk_form(self.ctx, typ)
+        if rc < 0:
+            check(rc)
+        return rc
+
     def set_q1_shape(self, shape: int):
         """Logits row-stats block shape (include/lac.h LAC_OPT_Q1_SHAPE; identical
         results, only speed differs): 0 auto, 1..4 / 6 / 8 / 10 / 14 / 15 / 17 / 18

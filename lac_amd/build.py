@@ -1,8 +1,8 @@
 """Build liblac.so in-tree for gfx950:  python -m lac_amd.build [--force]
 
-The library is nine translation units (csrc/lac_api.hip, lac_encode.hip,
+The library is ten translation units (csrc/lac_api.hip, lac_encode.hip,
 lac_decode.hip, lac_logits.hip, lac_fsm.hip, lac_count.hip,
-lac_history.hip, lac_ranges.hip, lac_sparse.hip) over shared headers (csrc/*.h, include/*.h),
+lac_history.hip, lac_ranges.hip, lac_sparse.hip, lac_topk.hip) over shared headers (csrc/*.h, include/*.h),
 compiled in parallel to objects under csrc/_obj/ and linked into lac_amd/liblac.so.
 An object is rebuilt when its source or any header is newer.  Variants for A/B
 runs: build(out=..., extra=("-DLAC_...=0",)) compiles into their own object

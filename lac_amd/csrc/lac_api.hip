@@ -150,6 +150,10 @@ int lac_set_option(lac_ctx *c, int option, int64_t value) {
         if (value < Q1_STEP_AUTO || value > Q1_STEP_SPLIT) return fail(LAC_E_ARG, "q1 step mode: 0, 1 or 2");
         c->q1_step = (int)value;
         return LAC_OK;
+    case LAC_OPT_TOPK_FORM:
+        if (value < 0 || value > 2) return fail(LAC_E_ARG, "top-k form: 0, 1 or 2");
+        c->topk_form = (int)value;
+        return LAC_OK;
     case LAC_OPT_MAPPING:
         if (value != LAC_MAP_CEIL && value != LAC_MAP_FLOOR) return fail(LAC_E_ARG, "bad mapping");
         c->mapping = (int)value;

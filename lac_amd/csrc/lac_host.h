@@ -60,6 +60,7 @@ struct lac_ctx {
     int cus = 256;                      // compute units (persistent grids)
     int q1_shape = 0;                   // logits stats block shape (0 auto; lac_set_option tuning)
     int q1_step = 0;                    // LAC_OPT_Q1_STEP: the one-position logits calls (0 auto, 1 fused, 2 two launches)
+    int topk_form = 0;                  // LAC_OPT_TOPK_FORM: lac_topk_logits' kernel form (0 auto, 1 registers, 2 streamed)
     uint64_t *q1chunks = nullptr;       // logits / stats-path decode: [chunk_steps * B][64] chunk totals
     void *dmeta = nullptr;              // stats-path decode: [chunk_steps * B] DecRowMeta
     int64_t *dresume = nullptr;         //                    [B] first step k_decode_lean left

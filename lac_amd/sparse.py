@@ -6,6 +6,7 @@ and one integer ``base``; it stands for the dense table ``pmf[s] = base + wt_j w
 
 * :func:`dense_rows`      the dense uint64 rows, for checking and for users of the table paths
 * :func:`topk_rows`       sparse rows from logits: the top k, a floor under the rest
+* :func:`topk_rows_q1`    the same from one kernel and an integer-exact rule (BatchCoder.topk_logits)
 * :class:`TopKCompressor` batched LLM compression that codes each position's top-k row
 """
 from __future__ import annotations
@@ -75,6 +76,26 @@ def topk_rows(logits, k, weight_bits=24, base=1, prec=48):
     return idx, w, base
 
 
+def topk_rows_q1(coder, logits, k, weight_bits=24, base=1):
+    """Sparse rows of logits by the integer-exact q1 rule, in one launch
+    (:meth:`lac_amd.batch.BatchCoder.topk_logits`, include/lac.h lac_topk_logits): the k heaviest
+    q1 entries per row, the lower symbol first among equal weights, ``wt = TAB[544 - level] >>
+    (24 - weight_bits)``; K is k rounded up to a multiple of 4, padded with -1.
+    -> (idx int32 [steps, streams, K], wt int32 bit patterns [steps, streams, K], base).  Raises as
+    :func:`topk_rows` does if ``base * V + K * 2^weight_bits`` exceeds 2^(prec-1) of the coder."""
+    V, k, weight_bits, base = coder.vocab, int(k), int(weight_bits), int(base)
+    if not 1 <= k <= min(V, 256):
+        raise ValueError(f"k = {k}: between 1 and min(V, 256)")
+    if not 0 <= weight_bits <= 24 or not 1 <= base < 1 << 32:
+        raise ValueError("weight_bits in [0, 24], base in [1, 2^32)")
+    K = (k + 3) // 4 * 4
+    if base * V + K * (1 << weight_bits) > 1 << (coder.prec - 1):
+        raise ValueError(f"base * V + K * 2^weight_bits = {base * V + K * (1 << weight_bits)} exceeds 2^(prec-1) = "
+                         f"2^{coder.prec - 1}: lower weight_bits or base, or raise prec")
+    idx, wt = coder.topk_logits(logits, k, weight_bits, K)
+    return idx, wt, base
+
+
 class TopKCompressor:
     """Batched LLM compression over top-k rows: step t codes token t under the sparse row of the
     model's logits after ``[BOS] + tokens[:, :t]`` -- the k most likely tokens by their weights,
@@ -82,9 +103,13 @@ class TopKCompressor:
     ``lac_amd.llm.TinyCausalLM``): one cached model step per position on both sides,
     ``encode_sparse`` on compress and a one-step ``decode_sparse`` on decompress, so a position
     moves 8 K bytes to the coder where a dense row moves 8 V.  Both sides compute the rows the
-    same way from bit-identical logits, so the code is lossless."""
+    same way from bit-identical logits, so the code is lossless.  ``rule``: "float" (default) builds
+    the rows with :func:`topk_rows` (torch.topk and a float64 exp on the device); "q1" builds them
+    with :func:`topk_rows_q1`, one kernel and an integer-exact rule that does not depend on the
+    platform's floating point or on how torch.topk breaks ties (weight_bits <= 24; the model's
+    logits must be bf16 or f32 with a vocabulary that is a multiple of 8 or 4)."""
 
-    def __init__(self, module, vocab, k, weight_bits=24, base=1, prec=48, bos=1, device="cuda"):
+    def __init__(self, module, vocab, k, weight_bits=24, base=1, prec=48, bos=1, device="cuda", rule="float"):
         import torch
         if not (hasattr(module, "step") and hasattr(module, "init_cache")):
             raise TypeError("TopKCompressor needs an incremental module (init_cache / step)")
@@ -92,20 +117,37 @@ class TopKCompressor:
         self.vocab, self.k, self.weight_bits, self.base = int(vocab), int(k), int(weight_bits), int(base)
         self.prec, self.bos = int(prec), int(bos)
         self.device = torch.device(device)
+        if rule not in ("float", "q1"):
+            raise ValueError('rule: "float" or "q1"')
+        if rule == "q1" and not 0 <= self.weight_bits <= 24:
+            raise ValueError('rule "q1": weight_bits in [0, 24]')
+        self.rule = rule
         K = (self.k + 3) // 4 * 4
         if self.base * self.vocab + K * (1 << self.weight_bits) > 1 << (self.prec - 1):
             raise ValueError("base * vocab + K * 2^weight_bits exceeds 2^(prec-1)")
 
-    def _steps(self, B, T, feed):
-        """yields (t, idx [1, B, K], wt [1, B, K]) for t < T; feed(t) -> the tokens [B] fed at t + 1."""
+    def _row(self, lg, coder):
+        """the sparse rows (idx [1, B, K], wt [1, B, K]) of one position's logits [B, V]"""
+        import torch
+        if self.rule == "q1":
+            if lg.dtype not in (torch.bfloat16, torch.float32):
+                lg = lg.float()
+            idx, wt, _ = topk_rows_q1(coder, lg.contiguous(), self.k, self.weight_bits, self.base)
+            return idx, wt
+        idx, wt, _ = topk_rows(lg, self.k, self.weight_bits, self.base, self.prec)
+        return idx[None], wt[None]
+
+    def _steps(self, B, T, feed, coder=None):
+        """yields (t, idx [1, B, K], wt [1, B, K]) for t < T; feed(t) -> the tokens [B] fed at t + 1.
+        ``coder``: the B-stream coder whose topk_logits builds the rows under rule "q1"."""
         import torch
         cache = self.module.init_cache(B, T)
         tok = torch.full((B,), self.bos, dtype=torch.long, device=self.device)
         for t in range(T):
             with torch.no_grad():
                 lg = self.module.step(tok, cache, t)[:, :self.vocab]
-            idx, wt, _ = topk_rows(lg, self.k, self.weight_bits, self.base, self.prec)
-            yield t, idx[None], wt[None]
+            idx, wt = self._row(lg, coder)
+            yield t, idx, wt
             tok = feed(t)
             tok = torch.where(tok < 0, torch.full_like(tok, self.bos), tok)   # (a failed stream's -1: raised at the end)
 
@@ -114,7 +156,12 @@ class TopKCompressor:
         import torch
         tokens = tokens.to(self.device, torch.long)
         B, T = tokens.shape
-        got = [(i, w) for _, i, w in self._steps(B, T, lambda t: tokens[:, t])]
+        coder = self._coder(B, T) if self.rule == "q1" else None
+        try:
+            got = [(i, w) for _, i, w in self._steps(B, T, lambda t: tokens[:, t], coder)]
+        finally:
+            if coder is not None:
+                coder.close()
         return torch.cat([i for i, _ in got], 0), torch.cat([w for _, w in got], 0), self.base
 
     def _coder(self, B, T):
@@ -131,7 +178,7 @@ class TopKCompressor:
         coder = self._coder(B, T)
         try:
             coder.reset()
-            for t, idx, wt in self._steps(B, T, lambda t: tokens[:, t]):
+            for t, idx, wt in self._steps(B, T, lambda t: tokens[:, t], coder):
                 coder.encode_sparse(idx, wt, self.base, sym[t:t + 1])
             coder.finish()
             coder.raise_on_error()
@@ -152,7 +199,7 @@ class TopKCompressor:
             coder.decode_open(torch.from_numpy(buf).to(self.device),
                               torch.as_tensor(np.asarray(nbits, dtype=np.int64), device=self.device))
             out = torch.empty((B, T), dtype=torch.long, device=self.device)
-            for t, idx, wt in self._steps(B, T, lambda t: out[:, t]):
+            for t, idx, wt in self._steps(B, T, lambda t: out[:, t], coder):
                 out[:, t] = coder.decode_sparse(idx, wt, self.base)[0].to(torch.long)
             coder.raise_on_error()
             return out
